@@ -2,6 +2,12 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--encoder vitl] [--frames 32] [--size 518 518]
     python bench.py --video [--gpus N] ...      # BASELINE configs[3]: a 176-frame video, 8 windows
+    python bench.py --full ...                  # also the roofline probe and the CPU baseline (below)
+    python bench.py --dump-outputs DIR ...      # write the last timed step's outputs as DIR/<name>.npy
+
+A plain run sets up, warms up, times ``--steps`` steps (``ms_per_step`` = the timed region / steps), writes
+its outputs if ``--dump-outputs`` is given and prints one JSON line; ``roofline`` and ``cpu_baseline`` are
+null in it.  ``--full`` adds the two legs under "Extra fields" below (minutes, not seconds).
 
 Default mode (BASELINE.json configs[2], and configs[3]'s clip-parallel form for N > 1): a step is one
 ``VideoDepthAnything.forward`` of a [1, 32, 3, 518, 518] clip (ViT-L fp16, full HIP path) on every
@@ -21,7 +27,15 @@ step is still one whole forward, all inside the timed region.
 ranks, depth resize, per-round RCCL gather to rank 0, host scale/shift stitching) -- all inside the
 timed region.  value = video frames / s ("scaling": "strong": the video is fixed as N grows).
 
-Extra fields:
+``--dump-outputs DIR``: after the timed steps, rank 0 writes what the last timed step returned to its
+caller as float32 ``DIR/<name>.npy`` (``depth``: the clip's [clips, T, H, W] depth, or the video's
+[frames, H, W]; with the RCCL gather also ``depth_rank<r>`` for r > 0, the other ranks' clips as rank 0
+received them).  The files take at most 64 MB in all, shared smallest array first; an array past its
+share of what is left is written as a fixed, seeded sample of its elements
+(``<name>.npy`` holds the values, ``<name>_index.npy`` their flat int64 indices, ``<name>_shape.npy`` the
+full shape).  Inputs and weights are seeded, so two runs with the same arguments dump the same inputs' outputs.
+
+Extra fields, measured with ``--full`` only:
   roofline      dominant kernel = encoder MLP fc1 GEMM + GELU, timed per launch with HIP events on its
                 launch stream (inside the timed region with one clip in flight; with several, over
                 single-stream forwards right after it, see roofline.probe); achieved = algorithmic FLOPs per launch / mean
@@ -53,7 +67,7 @@ GFLOP_PER_FRAME = {("vitl", 518, 518): 1404.6, ("vits", 518, 518): 121.3, ("vitl
 PROFILE_ROUND = "r06"      # profiles/<round>_pmc_*.json carry the PMC figures quoted in the line
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
@@ -65,9 +79,15 @@ def parse():
     ap.add_argument("--video", action="store_true", help="time infer_video_depth on a synthetic video (configs[3])")
     ap.add_argument("--video-frames", type=int, default=176, help="frames of the --video input (176 = 8 windows)")
     ap.add_argument("--cpu-baseline-frames", type=int, default=32,
-                    help="frames of the CPU-oracle clip timed as the cpu_baseline (0 disables; the default is the "
+                    help="--full: frames of the CPU-oracle clip timed as the cpu_baseline (0 disables; the default is the "
                          "whole 32-frame clip of the workload, ~80 s on the box's 16 threads)")
-    ap.add_argument("--no-probe", action="store_true", help="skip the per-launch event probe")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: the fc1 roofline probe and the CPU-oracle "
+                         "baseline (off by default: a plain run only sets up, warms up, times the steps and prints)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32; "
+                         "a fixed seeded sample of an array past the 64 MB budget)")
+    ap.add_argument("--no-probe", action="store_true", help="--full: skip the per-launch event probe")
     ap.add_argument("--graph", action="store_true", help="replay the forward as a captured HIP graph")
     ap.add_argument("--streams", type=int, default=2,
                     help="clips in flight per GPU: step i runs on HIP stream i %% streams (the fc1 roofline "
@@ -79,7 +99,10 @@ def parse():
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU-only rehearsal of the launch / gather / timing plumbing with a stand-in forward "
                          "(tests; the line it prints is not a measurement)")
-    return ap.parse_args()
+    args = ap.parse_args(argv)
+    if not args.full:  # a plain run: the headline figure only
+        args.no_probe, args.cpu_baseline_frames = True, 0
+    return args
 
 
 class _StandIn(torch.nn.Module):
@@ -104,6 +127,35 @@ def relaunch(args) -> int:
            "--master-addr", "127.0.0.1", f"--master-port={port}", os.path.abspath(__file__)] + sys.argv[1:]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     return subprocess.call(cmd, env=env)
+
+
+DUMP_BUDGET = 64 * 1000 * 1000  # bytes --dump-outputs may write in all
+DUMP_SEED = 20240
+
+
+def dump_outputs(dirname, arrays):
+    """Write {name: tensor | ndarray} as float32 DIR/<name>.npy within DUMP_BUDGET bytes in all.  The
+    budget is shared smallest array first: an array that fits an equal share of what is left is written
+    whole (so small arrays leave their unused share to the large ones), one that does not is written as
+    a seeded sample of that share (values, flat indices, full shape)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {name: np.ascontiguousarray(a.detach().float().cpu().numpy() if isinstance(a, torch.Tensor) else a,
+                                         dtype=np.float32) for name, a in arrays.items()}
+    left = DUMP_BUDGET
+    order = sorted(arrays, key=lambda name: arrays[name].nbytes)
+    for i, name in enumerate(order):
+        a = arrays[name]
+        share = left // (len(order) - i)
+        left -= min(share, a.nbytes + 4096)
+        if a.nbytes + 4096 <= share:  # (4096: room for the .npy headers)
+            np.save(os.path.join(dirname, f"{name}.npy"), a)
+            continue
+        k = (share - 4096) // 12  # 4 bytes of value + 8 of index per element, headers aside
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, size=k, replace=False)).astype(np.int64)
+        np.save(os.path.join(dirname, f"{name}.npy"), a.reshape(-1)[idx])
+        np.save(os.path.join(dirname, f"{name}_index.npy"), idx)
+        np.save(os.path.join(dirname, f"{name}_shape.npy"), np.asarray(a.shape, dtype=np.int64))
 
 
 def cpu_model() -> str:
@@ -290,6 +342,11 @@ def main():
         got = gbufs[(args.steps - 1) % 2]
         if not all(bool(torch.isfinite(t).all()) for t in got):
             raise RuntimeError("non-finite gathered depth")
+    if args.dump_outputs and rank == 0:
+        out = {"depth": depth}
+        if gather and nccl:  # (rank 0's own clip is ``depth``: not written twice)
+            out.update({f"depth_rank{r}": t for r, t in enumerate(gbufs[(args.steps - 1) % 2]) if r > 0})
+        dump_outputs(args.dump_outputs, out)
     probe_steps = 0
     if probe and not live:  # the same forward, one clip at a time, after the timed region
         probe_steps = min(args.steps, 10)
@@ -437,6 +494,8 @@ def run_video(args, model, dev, rank, world, n_dev, tdist):
     if rank == 0:
         if depth.shape != (n, H, W) or not np.isfinite(depth).all():
             raise RuntimeError(f"bad video depth {depth.shape}")
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"depth": depth})
         value = args.steps * n / elapsed
         line = {
             "metric": f"video depth frames/sec, {n}-frame {H}x{W} video ({nwin} windows of 32), "
