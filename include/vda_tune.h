@@ -18,11 +18,8 @@ extern "C" {
  * the halo conv; 10 + cfg = implicit-GEMM depth tail). */
 int vda_debug_force_tile(int32_t cfg);
 /* Phased 256-row GEMM: persist_blocks > 0 launches that many persistent blocks (0 = one block per tile,
- * -1 = automatic: one per CU); stagger_ticks >= 0 forces the start delay (100 MHz ticks) of the delayed
- * half of the blocks, -1 = automatic (none), -2 = half a tile when the last round is short. */
-int vda_debug_gemm_sched(int32_t persist_blocks, int32_t stagger);
-/* groups > 1: every phased-GEMM block starts ((block / 8) % groups) / groups of the stagger ticks late. */
-int vda_debug_gemm_desync(int32_t groups);
+ * -1 = automatic: one per CU). */
+int vda_debug_gemm_sched(int32_t persist_blocks);
 /* 1: the residual + row-statistics GEMMs (proj / fc2) through the register epilogue (bit-identical;
  * measured slower than the staged epilogue the product uses); 0 = staged. */
 int vda_debug_gemm_epi(int32_t res_register);
@@ -35,8 +32,6 @@ int vda_debug_hconv(int32_t mode);
 /* Depth tail: -1 = automatic (the 2-blocks-per-CU depth conv with the resize fused), 2 = the same conv on
  * a materialised resize (bit-identical; needs the workspace), 0 = the older 8-wave halo kernels. */
 int vda_debug_dconv(int32_t mode);
-/* fused depth conv: the second half of its grid starts units1024 x 1024 shader cycles late (0 = off) */
-int vda_debug_dconv_stagger(int32_t units1024);
 /* Attention kernels: spatial 1 = the round-1 16x16x32 kernel; temporal 1 = the direct-load kernel. */
 int vda_debug_attn(int32_t spatial_old, int32_t temporal_old);
 

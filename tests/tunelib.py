@@ -27,8 +27,7 @@ def tune_lib():
 
 
 class TuneLib:
-    DEFAULTS = dict(force_tile=-1, strip_split=0, hconv=-1, dconv=-1, gemm_epi=0, attn=(0, 0), gemm_sched=(-1, -1),
-                    gemm_desync=0)
+    DEFAULTS = dict(force_tile=-1, strip_split=0, hconv=-1, dconv=-1, gemm_epi=0, attn=(0, 0), gemm_sched=-1)
 
     def __init__(self, path):
         self.lib = ctypes.CDLL(path)

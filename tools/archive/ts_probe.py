@@ -6,8 +6,8 @@ import numpy as np, torch
 from vda_amd import ops, _lib
 from vda_amd._lib import ACT_GELU
 L = _lib.lib()
-def probe(M, N, K, act, sched=(-1, 0)):
-    L.vda_debug_gemm_sched(*sched)
+def probe(M, N, K, act, sched=-1):
+    L.vda_debug_gemm_sched(sched)
     x = torch.rand(M, K, device="cuda", dtype=torch.float16) * 2 - 1
     w = (torch.randn(N, K, device="cuda") * K ** -0.5).half()
     b = torch.randn(N, device="cuda") * 0.1
@@ -20,7 +20,7 @@ def probe(M, N, K, act, sched=(-1, 0)):
     ts = buf[:256].astype(np.float64) / 100.0  # us
     v = ts[(ts[:, 0] > 0)]
     d = np.diff(v, axis=1)
-    names = ["stagger", "prologue", "mainloop", "epi-ph1", "epi-ph2", "drain", "tail"]
+    names = ["setup", "prologue", "mainloop", "epi-ph1", "epi-ph2", "drain", "tail"]
     med = np.median(d, axis=0)
     print(f"{M}x{N}x{K} act{act} sched{sched}: blocks {len(v)}  start spread {v[:,0].max()-v[:,0].min():.1f}us  "
           + "  ".join(f"{n}={m:.2f}" for n, m in zip(names, med)) + f"  tile={np.median(v[:,7]-v[:,0]):.2f}", flush=True)

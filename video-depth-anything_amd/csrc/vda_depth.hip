@@ -18,8 +18,7 @@
 // s_barrier per step.  LDS layouts: patch slot = pixel*CPX + (chunk ^ (pixel & 7)) (CPX = 8 chunks of
 // 16 B) resp. ^((pixel >> 1) & 3) (CPX = 4); weights row*CPX + (chunk ^ ((row >> 1) & (CPX-1))):
 // conflict-free for the ds_read_b128 lane groups at any patch offset (brute-forced).
-#include "vda_common.h"
-#include "../../include/vda.h"
+#include "vda_internal.h"
 
 namespace {
 
@@ -587,7 +586,7 @@ extern "C" int vda_debug_oc1_timestamps(void* host) {
 }
 #endif
 
-// called by vda_depth_head (vda_gemm.hip) after the resize into ws; returns 1 if the shape is not
+// called by vda_depth_head (vda_depth_head.hip) after the resize into ws; returns 1 if the shape is not
 // supported here (caller falls back to the implicit-GEMM kernel)
 int vda_depth_halo(const void* U, const void* w1, const float* b1, const float* w2, const float* b2, float* depth,
                    int BT, int H, int W, int C, hipStream_t st) {

@@ -30,8 +30,7 @@
 // quadrant, 2.6 VALU per MFMA against the dense GEMM's 1.7 (profiles/r04_pmc_conv_gemm.log); the 9-slot
 // stride leaves the ds_read_b128 lane groups 2-way conflicted at worst (10 slots would be conflict-free
 // but do not fit the LDS).
-#include "vda_common.h"
-#include "../../include/vda.h"
+#include "vda_internal.h"
 #include <type_traits>
 
 namespace {

@@ -1,6 +1,5 @@
 // Bilinear resize, patch-embed im2col, and the C-ABI error plumbing.
-#include "vda_common.h"
-#include "../../include/vda.h"
+#include "vda_internal.h"
 #include <cstdio>
 #include <cstring>
 
@@ -194,7 +193,7 @@ __global__ __launch_bounds__(256) void conv_im2col_kernel(const h16* __restrict_
 
 }  // namespace
 
-// A [BT*Ho*Wo, ks*ks*Cin] for the explicit-im2col conv route (vda_gemm.hip); Cin % 8 == 0
+// A [BT*Ho*Wo, ks*ks*Cin] for the explicit-im2col conv route (vda_conv2d.hip); Cin % 8 == 0
 int vda_conv_im2col(const void* x, void* a, int BT, int H, int W, int Cin, int Ho, int Wo, int ks, int stride, int pad,
                     hipStream_t st) {
   const int M = BT * Ho * Wo, cpr = ks * ks * (Cin / 8);

@@ -1,6 +1,5 @@
 // LayerNorm / GroupNorm over token-major (NHWC) fp16 activations, fp32 statistics (gfx950).
-#include "vda_common.h"
-#include "../../include/vda.h"
+#include "vda_internal.h"
 
 namespace {
 

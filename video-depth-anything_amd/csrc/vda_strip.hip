@@ -21,8 +21,7 @@
 // slabs [s*nsl, (s+1)*nsl) and stores its fp32 partial tile into its own workspace slice with plain
 // stores; strip_finish_kernel adds the slices in a fixed order (deterministic) and applies the
 // epilogue.  The host picks the split count from a rounds x steps cost model (vda_conv_strip).
-#include "vda_common.h"
-#include "../../include/vda.h"
+#include "vda_internal.h"
 
 namespace {
 
