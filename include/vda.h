@@ -276,6 +276,37 @@ int vda_depth_resize(const float* depth, float* out, int32_t N, int32_t H, int32
                      int32_t wo, void* stream);
 
 /*
+ * Least-squares scale/shift of pred onto target over n elements, on the device:
+ *   a_00 = S m p^2, a_01 = S m p, a_11 = S m, b_0 = S m p t, b_1 = S m t   (m = mask, NULL = all ones)
+ *   det = a_00 a_11 - a_01^2
+ *   ss = (scale, shift) = ((a_11 b_0 - a_01 b_1) / det, (-a_01 b_0 + a_00 b_1) / det), or (1, 0) when det == 0.
+ * Every sum and the solve are fp64 in a fixed order (no atomics: the same input gives the same bits on
+ * every run); ss is rounded to fp32 on the store only.  sums [5] double (a_00, a_01, a_11, b_0, b_1) and
+ * ss [2] float are DEVICE memory; sums may be NULL.  pred / target: any 4-byte-aligned address, n >= 1.
+ * ws: vda_scale_shift_workspace(n) bytes of device memory, 8-byte aligned, owned by the caller; it needs
+ * no initialisation and holds nothing between calls.  No synchronisation: the result stays on the device.
+ * Replaces compute_scale_and_shift (utils/util.py:40-62) as called from video_depth.py:393-395 (long
+ * video) and :312-314 (streaming), which sum in fp32 on the host.
+ */
+int64_t vda_scale_shift_workspace(int64_t n);
+int vda_scale_shift(const float* pred, const float* target, const uint8_t* mask, int64_t n, double* sums,
+                    float* ss, void* ws, int64_t ws_bytes, void* stream);
+
+/*
+ * Resize + align + blend in one pass: per output pixel of out [F, ho, wo]
+ *   r = bilinear align_corners=True resize of src [F, H, W] (the arithmetic of vda_depth_resize)
+ *   v = r * ss[0] + ss[1]          (multiply and add rounded separately; ss DEVICE [2], NULL = identity)
+ *   v = v < 0 ? 0 : v              (when clip != 0)
+ *   out = pre * w_pre[f] + v * w_post[f]   (three roundings; pre [F, ho, wo] or NULL: out = v)
+ * w_pre / w_post: F floats each in HOST memory (needed with pre only); out may alias pre.  F <= 32.
+ * Replaces video_depth.py:371 + :400-413 with get_interpolate_frames (utils/util.py:65-73) for the long
+ * video and :299 + :315 for streaming (which does not clip).
+ */
+int vda_depth_align(const float* src, int32_t F, int32_t H, int32_t W, int32_t ho, int32_t wo, const float* ss,
+                    int32_t clip, const float* pre, const float* w_pre, const float* w_post, float* out,
+                    void* stream);
+
+/*
  * fp32 mode (infer_video_depth(fp32=True) / autocast off, video_depth.py:366-368): the same ops
  * with fp32 activations AND fp32 weights, fp32 accumulation on the exact-f32 MFMA
  * (v_mfma_f32_16x16x4_f32), exact-erf GELU, expf softmax.  Same layouts and epilogue contract as

@@ -9,6 +9,7 @@ Pillow formats; decord when installed), runs ``infer_video_depth`` (or ``infere_
 source / visualisation videos as .y4m, or .gif/.png/.webp via ``--vis_format``).  ``--synthetic_weights``
 uses the deterministic recipe of vda_amd.weights when no checkpoint is available (this image has none).
 ``--fp32`` selects the fp32 kernels (the reference's autocast-off path); the default is fp16 compute.
+``--stitch device`` aligns and stitches on the device (vda_scale_shift / vda_depth_align); the default is the host.
 """
 import argparse
 import os
@@ -51,6 +52,9 @@ def parse(argv=None):
     p.add_argument("--synthetic_weights", action="store_true")
     p.add_argument("--windows_per_batch", type=int, default=1,
                    help="windows per forward in the long-video path (2: ~3%% more frames/s on MI355X)")
+    p.add_argument("--stitch", type=str, default="host", choices=["host", "device"],
+                   help="where windows (or, with --process_single_image --align_each_new_frame, new frames) are "
+                        "aligned and stitched: on the host as the reference does, or on the device")
     a = p.parse_args(argv)
     assert a.inference_length > len(a.keyframe_list) + 2, "Inference length to small for the number of geiven keyframes"
     return a
@@ -78,11 +82,11 @@ def main(argv=None):
         depths, fps = model.infere_single_image(frames, target_fps, device=dev, fp32=args.fp32, input_size=args.input_size,
                                                 inference_length=args.inference_length, keyframe_list=args.keyframe_list,
                                                 align_each_new_frame=args.align_each_new_frame, warmup=True,
-                                                skip_tmp_block=args.skip_tmp_block)
+                                                skip_tmp_block=args.skip_tmp_block, stitch=args.stitch)
     else:
         depths, fps = model.infer_video_depth(frames, target_fps, input_size=args.input_size, device=dev, fp32=args.fp32,
                                               skip_tmp_block=args.skip_tmp_block and not args.original,
-                                              windows_per_batch=max(1, args.windows_per_batch))
+                                              windows_per_batch=max(1, args.windows_per_batch), stitch=args.stitch)
     dur = time.time() - t0
     os.makedirs(args.output_dir, exist_ok=True)
     stem = os.path.splitext(os.path.basename(args.input_video))[0]

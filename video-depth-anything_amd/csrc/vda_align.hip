@@ -1,0 +1,217 @@
+// Scale/shift alignment of depth windows on the device: the least-squares statistics and the
+// resize + affine + clip + blend pass around them.
+//
+// scale_shift: compute_scale_and_shift (utils/util.py:40-62) as video_depth.py:393-395 (long video)
+// and :312-314 (streaming) call it: five masked sums over pred / target and the 2x2 solve.  The
+// reference sums in fp32 in numpy's pairwise order; here every sum is fp64 in a fixed order
+// (per thread -> wave butterfly -> block in wave order -> per-block partials in the caller's
+// workspace -> one wave adds the partials in index order and solves), so the result is the same bits
+// on every run and no atomics are involved.  HBM-bound: 8 B (9 B with a mask) per element.
+//
+// depth_align: video_depth.py:371 / :299 (resize) + :400-413 / :315 (affine, clip) + get_interpolate_frames
+// (utils/util.py:65-73, blend) in one pass, one thread per output pixel: the resized, unaligned
+// window is never written to HBM.  4 B read (through L1/L2) + 4 B written per element, + 4 B with a blend.
+#include "vda_common.h"
+#include "../../include/vda.h"
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kWaves = kBlock / 64;
+constexpr int64_t kElemsPerBlock = (int64_t)kBlock * 4;  // one 16-byte load per thread and iteration
+
+// 16-byte groups of floats / 4-byte groups of mask bytes whose address is only element-aligned: target
+// and mask share pred's head, so their body loads start wherever that leaves them
+typedef float f4a4 __attribute__((ext_vector_type(4), aligned(4)));
+typedef uint8_t u8x4a1 __attribute__((ext_vector_type(4), aligned(1)));
+
+struct Sums {
+  double v[5];  // a_00 = S m p^2, a_01 = S m p, a_11 = S m, b_0 = S m p t, b_1 = S m t
+};
+
+__device__ __forceinline__ void accumulate(Sums& s, float p, float t, float m) {
+  const double dp = (double)p, dt = (double)t, dm = (double)m;
+  const double mp = dm * dp;  // exact: a product of two fp32 values
+  s.v[0] = fma(mp, dp, s.v[0]);
+  s.v[1] += mp;
+  s.v[2] += dm;
+  s.v[3] = fma(mp, dt, s.v[3]);
+  s.v[4] = fma(dm, dt, s.v[4]);
+}
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+int scale_shift_grid(int64_t n) {
+  const int64_t want = (n + kElemsPerBlock - 1) / kElemsPerBlock;
+  const int64_t cap = 4 * (int64_t)vda_cu_count();
+  return (int)(want < 1 ? 1 : (want > cap ? cap : want));
+}
+
+// Block b leaves its five sums in part[b * 5 .. b * 5 + 4].  head = elements before pred's first
+// 16-byte boundary, nvec = 16-byte groups after it; block 0 also takes the head and the tail.
+template <bool MASK>
+__global__ __launch_bounds__(kBlock) void scale_shift_partial_kernel(const float* __restrict__ pred,
+                                                                     const float* __restrict__ target,
+                                                                     const uint8_t* __restrict__ mask, int64_t n,
+                                                                     int head, int64_t nvec, double* __restrict__ part) {
+  Sums s = {{0., 0., 0., 0., 0.}};
+  const float* pb = pred + head;
+  const float* tb = target + head;
+  const uint8_t* mb = MASK ? mask + head : nullptr;
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < nvec; i += stride) {
+    const f4 p = *reinterpret_cast<const f4*>(pb + 4 * i);
+    const f4a4 t = *reinterpret_cast<const f4a4*>(tb + 4 * i);
+    float m[4] = {1.f, 1.f, 1.f, 1.f};
+    if (MASK) {
+      const u8x4a1 mv = *reinterpret_cast<const u8x4a1*>(mb + 4 * i);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) m[j] = (float)mv[j];
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) accumulate(s, p[j], t[j], m[j]);
+  }
+  if (blockIdx.x == 0) {
+    const int64_t tail0 = head + 4 * nvec;
+    const int tail = (int)(n - tail0);  // 0..3
+    int64_t e = -1;
+    if ((int)threadIdx.x < head) e = threadIdx.x;
+    else if ((int)threadIdx.x >= 8 && (int)threadIdx.x - 8 < tail) e = tail0 + (threadIdx.x - 8);
+    if (e >= 0) accumulate(s, pred[e], target[e], MASK ? (float)mask[e] : 1.f);
+  }
+  __shared__ double red[kWaves][5];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int j = 0; j < 5; ++j) {
+    const double w = wave_sum_f64(s.v[j]);
+    if (lane == 0) red[wave][j] = w;
+  }
+  __syncthreads();
+  if (threadIdx.x < 5) {
+    double a = red[0][threadIdx.x];
+#pragma unroll
+    for (int w = 1; w < kWaves; ++w) a += red[w][threadIdx.x];
+    part[(int64_t)blockIdx.x * 5 + threadIdx.x] = a;
+  }
+}
+
+// One wave: lane l adds partials l, l + 64, ... in index order, a butterfly adds the lanes, lane 0
+// solves the 2x2 system in fp64 (the plain closed form, no contraction) and rounds once on the store.
+__global__ __launch_bounds__(64) void scale_shift_solve_kernel(const double* __restrict__ part, int nparts,
+                                                               double* __restrict__ sums, float* __restrict__ ss) {
+  double a[5] = {0., 0., 0., 0., 0.};
+  for (int b = threadIdx.x; b < nparts; b += 64) {
+#pragma unroll
+    for (int j = 0; j < 5; ++j) a[j] += part[(int64_t)b * 5 + j];
+  }
+#pragma unroll
+  for (int j = 0; j < 5; ++j) a[j] = wave_sum_f64(a[j]);
+  if (threadIdx.x == 0) {
+#pragma clang fp contract(off)
+    const double a00 = a[0], a01 = a[1], a11 = a[2], b0 = a[3], b1 = a[4];
+    const double det = a00 * a11 - a01 * a01;
+    double x0 = 1., x1 = 0.;
+    if (det != 0.) {
+      x0 = (a11 * b0 - a01 * b1) / det;
+      x1 = (-a01 * b0 + a00 * b1) / det;
+    }
+    if (sums) {
+#pragma unroll
+      for (int j = 0; j < 5; ++j) sums[j] = a[j];
+    }
+    ss[0] = (float)x0;
+    ss[1] = (float)x1;
+  }
+}
+
+// numpy's `d * scale + shift` and `pre * (1 - w) + post * w` on float32 arrays round every multiply
+// and every add on its own; a contracted fma would not match them.
+__device__ __forceinline__ float affine_rn(float r, float scale, float shift) {
+#pragma clang fp contract(off)
+  const float m = r * scale;
+  return m + shift;
+}
+__device__ __forceinline__ float blend_rn(float pre, float w_pre, float post, float w_post) {
+#pragma clang fp contract(off)
+  const float a = pre * w_pre;
+  const float b = post * w_post;
+  return a + b;
+}
+
+constexpr int kMaxAlignFrames = 32;
+struct BlendArgs {
+  float w_pre[kMaxAlignFrames];
+  float w_post[kMaxAlignFrames];
+};
+
+// pre and out may be the same buffer: every thread reads its own pre element before it stores.
+__global__ __launch_bounds__(256) void depth_align_kernel(const float* __restrict__ src, const float* __restrict__ ss,
+                                                          const float* pre, float* out, int H, int W, int ho, int wo,
+                                                          int clip, BlendArgs ba) {
+  const int ox = blockIdx.x * 256 + threadIdx.x;
+  const int oy = blockIdx.y;
+  const int n = blockIdx.z;
+  if (ox >= wo) return;
+  float v = depth_bilinear_ac(src + (size_t)n * H * W, H, W, ho, wo, oy, ox);
+  if (ss) v = affine_rn(v, ss[0], ss[1]);
+  if (clip) v = v < 0.f ? 0.f : v;
+  const size_t o = ((size_t)n * ho + oy) * wo + ox;
+  if (pre) v = blend_rn(pre[o], ba.w_pre[n], v, ba.w_post[n]);
+  out[o] = v;
+}
+
+}  // namespace
+
+extern "C" int64_t vda_scale_shift_workspace(int64_t n) {
+  if (n < 1) return 0;
+  return ((int64_t)scale_shift_grid(n) * 5 * (int64_t)sizeof(double) + 255) / 256 * 256;
+}
+
+extern "C" int vda_scale_shift(const float* pred, const float* target, const uint8_t* mask, int64_t n, double* sums,
+                               float* ss, void* ws, int64_t ws_bytes, void* stream) {
+  VDA_CHECK_ARG(pred && target && ss && ws, "null pointer");
+  VDA_CHECK_ARG(n >= 1, "scale_shift needs n >= 1");
+  VDA_CHECK_ARG(((uintptr_t)pred & 3) == 0 && ((uintptr_t)target & 3) == 0 && ((uintptr_t)ws & 7) == 0 &&
+                    ((uintptr_t)sums & 7) == 0 && ((uintptr_t)ss & 3) == 0,
+                "pred / target / ss must be 4-byte aligned, sums and the workspace 8-byte aligned");
+  VDA_CHECK_ARG(ws_bytes >= vda_scale_shift_workspace(n), "workspace smaller than vda_scale_shift_workspace(n)");
+  const int grid = scale_shift_grid(n);
+  int64_t head = (int64_t)((16 - ((uintptr_t)pred & 15)) & 15) / 4;
+  if (head > n) head = n;
+  const int64_t nvec = (n - head) / 4;
+  double* part = (double*)ws;
+  if (mask)
+    hipLaunchKernelGGL(scale_shift_partial_kernel<true>, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, pred, target,
+                       mask, n, (int)head, nvec, part);
+  else
+    hipLaunchKernelGGL(scale_shift_partial_kernel<false>, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, pred, target,
+                       mask, n, (int)head, nvec, part);
+  VDA_LAUNCH_CHECK();
+  hipLaunchKernelGGL(scale_shift_solve_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double*)part, grid, sums,
+                     ss);
+  VDA_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int vda_depth_align(const float* src, int32_t F, int32_t H, int32_t W, int32_t ho, int32_t wo, const float* ss,
+                               int32_t clip, const float* pre, const float* w_pre, const float* w_post, float* out,
+                               void* stream) {
+  VDA_CHECK_ARG(src && out, "null pointer");
+  VDA_CHECK_ARG(F > 0 && H > 0 && W > 0 && ho > 0 && wo > 0, "empty depth geometry");
+  VDA_CHECK_ARG(F <= kMaxAlignFrames, "depth_align takes F <= 32 frames per call");
+  VDA_CHECK_ARG(ho <= 65535, "output height exceeds the launch grid");
+  VDA_CHECK_ARG(!pre || (w_pre && w_post), "a blend (pre) needs the host weight arrays w_pre and w_post");
+  BlendArgs ba;
+  for (int f = 0; f < kMaxAlignFrames; ++f) {
+    ba.w_pre[f] = pre && f < F ? w_pre[f] : 0.f;
+    ba.w_post[f] = pre && f < F ? w_post[f] : 0.f;
+  }
+  hipLaunchKernelGGL(depth_align_kernel, dim3((wo + 255) / 256, ho, F), dim3(256), 0, (hipStream_t)stream, src, ss, pre,
+                     out, H, W, ho, wo, clip ? 1 : 0, ba);
+  VDA_LAUNCH_CHECK();
+  return 0;
+}

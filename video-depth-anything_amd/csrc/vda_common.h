@@ -113,6 +113,21 @@ __device__ __forceinline__ uint4 bilerp8_mix(uint4 a, uint4 b, uint4 c, uint4 d,
   }
   return make_uint4(o[0], o[1], o[2], o[3]);
 }
+// One output pixel (oy, ox) of the fp32 depth resize of frame f [H, W] to (ho, wo), bilinear
+// align_corners=True (src = o * (in - 1) / (out - 1), torch upsample_bilinear2d).  The one definition
+// behind vda_depth_resize and vda_depth_align, so the two cannot drift.
+__device__ __forceinline__ float depth_bilinear_ac(const float* __restrict__ f, int H, int W, int ho, int wo, int oy,
+                                                   int ox) {
+  const float ry = ho > 1 ? (float)(H - 1) / (float)(ho - 1) : 0.f;
+  const float rx = wo > 1 ? (float)(W - 1) / (float)(wo - 1) : 0.f;
+  const float sy = ry * (float)oy, sx = rx * (float)ox;
+  const int y0 = (int)sy, x0 = (int)sx;
+  const int y1 = y0 + (y0 < H - 1 ? 1 : 0), x1 = x0 + (x0 < W - 1 ? 1 : 0);
+  const float ly = sy - (float)y0, lx = sx - (float)x0;
+  return (1.f - ly) * ((1.f - lx) * f[(size_t)y0 * W + x0] + lx * f[(size_t)y0 * W + x1]) +
+         ly * ((1.f - lx) * f[(size_t)y1 * W + x0] + lx * f[(size_t)y1 * W + x1]);
+}
+
 __device__ __forceinline__ float gelu_erf(float x) {
   return 0.5f * x * (1.0f + erf_fast(x * 0.70710678118654752f));
 }

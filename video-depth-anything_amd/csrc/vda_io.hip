@@ -81,17 +81,7 @@ __global__ __launch_bounds__(256) void depth_resize_kernel(const float* __restri
   const int oy = blockIdx.y;
   const int n = blockIdx.z;
   if (ox >= wo) return;
-  // align_corners=True: src = o * (in - 1) / (out - 1)  (torch upsample_bilinear2d)
-  const float ry = ho > 1 ? (float)(H - 1) / (float)(ho - 1) : 0.f;
-  const float rx = wo > 1 ? (float)(W - 1) / (float)(wo - 1) : 0.f;
-  const float sy = ry * (float)oy, sx = rx * (float)ox;
-  const int y0 = (int)sy, x0 = (int)sx;
-  const int y1 = y0 + (y0 < H - 1 ? 1 : 0), x1 = x0 + (x0 < W - 1 ? 1 : 0);
-  const float ly = sy - (float)y0, lx = sx - (float)x0;
-  const float* f = src + (size_t)n * H * W;
-  const float v = (1.f - ly) * ((1.f - lx) * f[(size_t)y0 * W + x0] + lx * f[(size_t)y0 * W + x1]) +
-                  ly * ((1.f - lx) * f[(size_t)y1 * W + x0] + lx * f[(size_t)y1 * W + x1]);
-  dst[((size_t)n * ho + oy) * wo + ox] = v;
+  dst[((size_t)n * ho + oy) * wo + ox] = depth_bilinear_ac(src + (size_t)n * H * W, H, W, ho, wo, oy, ox);
 }
 
 }  // namespace

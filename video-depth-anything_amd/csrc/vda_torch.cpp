@@ -500,6 +500,70 @@ Tensor depth_resize(const Tensor& depth, int64_t ho, int64_t wo) {
   return out;
 }
 
+// ---- scale/shift alignment ---------------------------------------------------------------------
+std::tuple<Tensor, Tensor> scale_shift(const Tensor& pred, const Tensor& target, OptT mask) {
+  TORCH_CHECK(pred.scalar_type() == at::kFloat && pred.is_contiguous() && pred.numel() >= 1,
+              "vda scale_shift: pred must be a contiguous, non-empty float tensor");
+  need_contig(target, at::kFloat, "target", pred);
+  TORCH_CHECK(target.numel() == pred.numel(), "vda scale_shift: pred and target must have the same number of elements");
+  if (mask) {
+    need_contig(*mask, at::kByte, "mask", pred);
+    TORCH_CHECK(mask->numel() == pred.numel(), "vda scale_shift: mask must have pred's number of elements");
+  }
+  Tensor ss = at::empty({2}, pred.options());
+  Tensor sums = at::empty({5}, pred.options().dtype(at::kDouble));
+  if (pred.is_meta()) return {ss, sums};
+  const at::OptionalDeviceGuard g(pred.device());
+  const int64_t n = pred.numel();
+  const int64_t wsb = vda_scale_shift_workspace(n);
+  Tensor ws = at::empty({wsb}, pred.options().dtype(at::kByte));
+  check_rc(vda_scale_shift((const float*)pred.data_ptr(), (const float*)target.data_ptr(), (const uint8_t*)ptr(mask), n,
+                           (double*)sums.data_ptr(), (float*)ss.data_ptr(), ws.data_ptr(), wsb, stream_of(pred)),
+           "vda_scale_shift");
+  return {ss, sums};
+}
+
+Tensor depth_align(const Tensor& src, int64_t ho, int64_t wo, OptT ss, bool clip, OptT pre,
+                   optional<at::ArrayRef<double>> w_pre, optional<at::ArrayRef<double>> w_post, OptT out_) {
+  TORCH_CHECK(src.scalar_type() == at::kFloat && src.dim() == 3 && src.is_contiguous(),
+              "vda depth_align: src must be a contiguous float [F, H, W] tensor");
+  const int64_t F = src.size(0), H = src.size(1), W = src.size(2);
+  TORCH_CHECK(F >= 1 && F <= 32, "vda depth_align: 1 <= F <= 32 frames per call, got ", F);
+  TORCH_CHECK(ho >= 1 && wo >= 1, "vda depth_align: empty output size");
+  if (ss) {
+    need_contig(*ss, at::kFloat, "ss", src);
+    TORCH_CHECK(ss->numel() == 2, "vda depth_align: ss must hold (scale, shift)");
+  }
+  float wp[32], wq[32];
+  if (pre) {
+    need_contig(*pre, at::kFloat, "pre", src);
+    TORCH_CHECK(pre->dim() == 3 && pre->size(0) == F && pre->size(1) == ho && pre->size(2) == wo,
+                "vda depth_align: pre must be [F, ho, wo]");
+    TORCH_CHECK(w_pre.has_value() && w_post.has_value() && (int64_t)w_pre->size() == F && (int64_t)w_post->size() == F,
+                "vda depth_align: a blend needs F weights in w_pre and in w_post");
+    for (int64_t f = 0; f < F; ++f) {
+      wp[f] = (float)(*w_pre)[f];
+      wq[f] = (float)(*w_post)[f];
+    }
+  }
+  Tensor out;
+  if (out_) {
+    need_contig(*out_, at::kFloat, "out", src);
+    TORCH_CHECK(out_->dim() == 3 && out_->size(0) == F && out_->size(1) == ho && out_->size(2) == wo,
+                "vda depth_align: out must be [F, ho, wo]");
+    out = *out_;
+  } else {
+    out = at::empty({F, ho, wo}, src.options());
+  }
+  if (src.is_meta()) return out;
+  const at::OptionalDeviceGuard g(src.device());
+  check_rc(vda_depth_align((const float*)src.data_ptr(), F, H, W, ho, wo, (const float*)ptr(ss), clip ? 1 : 0,
+                           (const float*)ptr(pre), pre ? wp : nullptr, pre ? wq : nullptr, (float*)out.data_ptr(),
+                           stream_of(src)),
+           "vda_depth_align");
+  return out;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(vda, m) {
@@ -526,6 +590,9 @@ TORCH_LIBRARY(vda, m) {
   m.def("depth_head(Tensor x, Tensor w1, Tensor b1, Tensor w2, Tensor b2, int Ho, int Wo) -> Tensor");
   m.def("preprocess_frames(Tensor frames, int H, int W, float[] mean, float[] std) -> Tensor");
   m.def("depth_resize(Tensor depth, int ho, int wo) -> Tensor");
+  m.def("scale_shift(Tensor pred, Tensor target, Tensor? mask=None) -> (Tensor ss, Tensor sums)");
+  m.def("depth_align(Tensor src, int ho, int wo, Tensor? ss=None, bool clip=True, Tensor? pre=None, "
+        "float[]? w_pre=None, float[]? w_post=None, Tensor(a!)? out=None) -> Tensor");
 }
 
 #define VDA_IMPL(KEY)                                         \
@@ -545,6 +612,8 @@ TORCH_LIBRARY(vda, m) {
     m.impl("depth_head", &depth_head);                        \
     m.impl("preprocess_frames", &preprocess_frames);          \
     m.impl("depth_resize", &depth_resize);                    \
+    m.impl("scale_shift", &scale_shift);                      \
+    m.impl("depth_align", &depth_align);                      \
   }
 
 VDA_IMPL(CUDA)

@@ -756,12 +756,14 @@ class VideoDepthAnything(nn.Module):
 
     def infere_single_image(self, frames, target_fps, input_size=518, device="cuda", fp32=False, warmup=True,
                             inference_length=32, keyframe_list=(0, 12), align_each_new_frame=True,
-                            skip_tmp_block=False):
-        """video_depth.py:91-327 on libvda (see vda_amd.stream); ``fp32`` selects the fp32 kernels."""
+                            skip_tmp_block=False, stitch="host"):
+        """video_depth.py:91-327 on libvda (see vda_amd.stream); ``fp32`` selects the fp32 kernels,
+        ``stitch="device"`` aligns each new frame on the device (no per-frame host copy of the alignment frames)."""
         from .stream import infere_single_image
         return infere_single_image(_StreamEngine(self, fp32), frames, target_fps, input_size=input_size, device=device,
                                    warmup=warmup, inference_length=inference_length, keyframe_list=keyframe_list,
-                                   align_each_new_frame=align_each_new_frame, skip_tmp_block=skip_tmp_block)
+                                   align_each_new_frame=align_each_new_frame, skip_tmp_block=skip_tmp_block,
+                                   stitch=stitch)
 
 
 class _StreamEngine:
@@ -780,14 +782,17 @@ class _StreamEngine:
 
 
 def _infer_video_depth(self, frames, target_fps, input_size=518, device="cuda", fp32=False, skip_tmp_block=False,
-                       windows_per_batch=1, rank=0, world=1, group=None, streams=2):
+                       windows_per_batch=1, rank=0, world=1, group=None, streams=2, stitch="host",
+                       return_device=False):
     """video_depth.py:329-417 on the MI355X forward (see vda_amd.video); ``fp32=True`` runs the
     fp32 kernels (the reference's autocast-off path), the default fp16 compute; ``streams``: window
-    batches in flight on one GPU (world == 1)."""
+    batches in flight on one GPU (world == 1); ``stitch="device"`` aligns and stitches on the device
+    (``return_device=True`` then returns a device tensor)."""
     from .video import infer_video_depth
     return infer_video_depth(lambda x: self.forward(x, skip_tmp_block, fp32=fp32), frames, target_fps, input_size=input_size,
                              device=device, windows_per_batch=windows_per_batch, rank=rank, world=world,
-                             group=group, streams=streams, prepare=lambda hw: self.prepare(device, hw, fp32))
+                             group=group, streams=streams, prepare=lambda hw: self.prepare(device, hw, fp32),
+                             stitch=stitch, return_device=return_device)
 
 
 VideoDepthAnything.infer_video_depth = _infer_video_depth

@@ -197,3 +197,41 @@ def depth_resize(depth: Tensor, ho: int, wo: int) -> Tensor:
     """depth [N, H, W] fp32 (GPU) -> [N, ho, wo] fp32, bilinear align_corners=True."""
     _need(depth, torch.float32, "depth")
     return _vda().depth_resize(depth, int(ho), int(wo))
+
+
+def scale_shift(pred: Tensor, target: Tensor, *, mask: Optional[Tensor] = None):
+    """Least-squares (scale, shift) of pred onto target (same number of elements, fp32, GPU; ``mask``
+    uint8 or None = all ones) -> (ss [2] fp32, sums [5] fp64 = a_00, a_01, a_11, b_0, b_1), both on the
+    device.  fp64 sums in a fixed order: deterministic, no host sync (vda.h vda_scale_shift)."""
+    _need(pred, torch.float32, "pred")
+    _need(target, torch.float32, "target")
+    if pred.numel() != target.numel() or pred.numel() < 1:
+        raise ValueError(f"pred and target need the same, non-zero number of elements, got {pred.numel()} and {target.numel()}")
+    if mask is not None:
+        _need(mask, torch.uint8, "mask")
+        if mask.numel() != pred.numel():
+            raise ValueError(f"mask has {mask.numel()} elements, pred {pred.numel()}")
+    return _vda().scale_shift(pred, target, mask)
+
+
+def depth_align(src: Tensor, ho: int, wo: int, *, ss: Optional[Tensor] = None, clip: bool = True,
+                pre: Optional[Tensor] = None, w_pre=None, w_post=None, out: Optional[Tensor] = None) -> Tensor:
+    """src [F, H, W] fp32 (GPU, F <= 32) -> [F, ho, wo]: bilinear align_corners=True resize (the bits
+    of ``depth_resize``), then ``* ss[0] + ss[1]`` (``ss`` a device [2] tensor, two roundings; None =
+    identity), then clip at 0, then with ``pre`` [F, ho, wo] the blend ``pre * w_pre[f] + v * w_post[f]``
+    (F Python floats each).  ``out`` may be ``pre`` (in place).  One pass (vda.h vda_depth_align)."""
+    _need(src, torch.float32, "src")
+    if src.dim() != 3 or not 1 <= src.shape[0] <= 32:
+        raise ValueError(f"src must be [F, H, W] with 1 <= F <= 32, got {tuple(src.shape)}")
+    if ss is not None:
+        _need(ss, torch.float32, "ss")
+    if pre is not None:
+        _need(pre, torch.float32, "pre")
+        if w_pre is None or w_post is None or len(w_pre) != src.shape[0] or len(w_post) != src.shape[0]:
+            raise ValueError("a blend (pre) needs one weight per frame in w_pre and in w_post")
+        w_pre, w_post = [float(v) for v in w_pre], [float(v) for v in w_post]
+    else:
+        w_pre = w_post = None
+    if out is not None:
+        _need(out, torch.float32, "out")
+    return _vda().depth_align(src, int(ho), int(wo), ss, bool(clip), pre, w_pre, w_post, out)

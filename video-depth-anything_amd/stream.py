@@ -19,7 +19,10 @@ Host/device split:
 * the engine does the model work: ``motion_features(x[1,3,H,W]) -> 4 maps`` and
   ``predict(x, context_maps, pred_idx, T, skip_tmp_block) -> (depth[P+1,H,W] fp32, 4 maps)``.
   ``VideoDepthAnything`` provides the libvda engine; ``oracle/vda_oracle.StreamEngine`` is the
-  CPU checker used by the tests.
+  CPU checker used by the tests;
+* the scale/shift alignment of each new frame runs on the host in the reference's numpy arithmetic
+  (the default), or with ``stitch="device"`` on the device (vda_scale_shift / vda_depth_align),
+  where the aligned frames later steps index stay in HBM and only the new frame is copied out.
 
 The reference's default configuration (``keyframe_list=[0, 12]`` with alignment) indexes feature
 slot ``inference_length`` out of a context of ``inference_length - 1`` rows at the first
@@ -35,7 +38,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 import torch
 
-from .video import DeviceIO, compute_scale_and_shift, net_input_size
+from .video import DeviceAlign, DeviceIO, compute_scale_and_shift, net_input_size
 
 
 @dataclass
@@ -104,16 +107,67 @@ class FeatureStore:
         return tuple(b.index_select(0, idx) for b in self.bufs)
 
 
+class _FrameRing:
+    """Emitted frames on their way to the host (``stitch="device"``): each frame is copied with a
+    non-blocking D2H copy into one of ``slots`` pinned staging frames and collected from there when
+    its slot comes round again, by which time the copy has long completed; the one real wait is
+    ``result`` at the end of the video.  On a CPU device the frames are taken as they are."""
+
+    def __init__(self, device: torch.device, slots: int = 8):
+        self.gpu = device.type == "cuda"
+        self.slots = [[None, None] for _ in range(slots)]  # [pinned frame, event of its pending copy]
+        self.count = 0
+        self.frames: List[np.ndarray] = []
+
+    def _collect(self, slot):
+        if slot[1] is not None:
+            slot[1].synchronize()
+            self.frames.append(slot[0].numpy().copy())
+            slot[1] = None
+
+    def push(self, frame: torch.Tensor):
+        if not self.gpu:
+            self.frames.append(frame.detach().to("cpu", torch.float32).numpy().copy())
+            return
+        slot = self.slots[self.count % len(self.slots)]
+        self.count += 1
+        self._collect(slot)
+        if slot[0] is None or slot[0].shape != frame.shape:
+            slot[0] = torch.empty(frame.shape, dtype=torch.float32, pin_memory=True)
+        slot[0].copy_(frame, non_blocking=True)
+        slot[1] = torch.cuda.Event()
+        slot[1].record()
+
+    def result(self) -> List[np.ndarray]:
+        for j in range(len(self.slots)):  # oldest first
+            self._collect(self.slots[(self.count + j) % len(self.slots)])
+        return self.frames
+
+
+def _resize_frames(align, depth: torch.Tensor, size: tuple) -> torch.Tensor:
+    """depth [F, H, W] -> [F, h, w] through ``align.depth_align`` (32 frames per call at the most)."""
+    parts = [align.depth_align(depth[c:c + 32], size, clip=False) for c in range(0, depth.shape[0], 32)]
+    return parts[0] if len(parts) == 1 else torch.cat(parts, 0)
+
+
 def infere_single_image(engine, frames, target_fps, input_size: int = 518, device="cuda", warmup: bool = True,
                         inference_length: int = 32, keyframe_list=(0, 12), align_each_new_frame: bool = True,
-                        skip_tmp_block: bool = False, io=DeviceIO):
+                        skip_tmp_block: bool = False, io=DeviceIO, stitch: str = "host", align=DeviceAlign):
     """Per-frame depth for ``frames`` (uint8 [N, h, w, 3]); returns (depth [N', h, w] float32, fps).
 
     video_depth.py:91-327: frames 0..L-2 only fill the feature store; from frame L-1 on every frame
     is predicted.  With alignment the first prediction emits the whole context's depths, later
     ones emit the new frame scaled/shifted onto the alignment frames, and the first emitted frame
     is dropped from the result (:322-323); without it one depth per predicted frame is emitted.
+
+    ``stitch="device"`` (with alignment; without it there is nothing to align and the host route runs):
+    the aligned frames that later steps index - frame 0 and the last ``n_slots`` - stay on the device,
+    every step runs ``align.scale_shift`` over the alignment frames and ``align.depth_align`` (no clip,
+    as :315) on the new frame, and only the new frame goes to the host, through a pinned ring with a
+    non-blocking copy; the host never waits on a per-frame copy of the P + 1 frames.
     """
+    if stitch not in ("host", "device"):
+        raise ValueError(f"stitch must be 'host' or 'device', got {stitch!r}")
     if not warmup:
         raise NotImplementedError  # video_depth.py:318-319
     if not isinstance(frames, torch.Tensor):
@@ -128,6 +182,10 @@ def infere_single_image(engine, frames, target_fps, input_size: int = 518, devic
     store: Optional[FeatureStore] = None
     depth_list: List[np.ndarray] = []
     emitted_first = False
+    on_device = stitch == "device" and align_each_new_frame
+    ring = _FrameRing(dev) if on_device else None
+    kept = {}    # device mode: emitted index -> aligned frame on the device (frame 0 and the last n_slots)
+    emitted = 0  # device mode: frames emitted so far
     for i in range(n):
         x = io.preprocess(frames[i:i + 1].to(dev), size)  # [1, 3, H, W]
         if i < L - 1:
@@ -159,6 +217,24 @@ def infere_single_image(engine, frames, target_fps, input_size: int = 518, devic
             store.put(i, maps)
         else:
             store.shift_in(maps, sch.drop_slot)
+        if on_device:
+            depth = depth.float()
+            if not emitted_first:
+                new = _resize_frames(align, depth, (fh, fw))
+                emitted_first = True
+            else:
+                P = len(pred_idx)
+                cur_kf = _resize_frames(align, depth[:P], (fh, fw))
+                old_kf = torch.stack([kept[j] for j in abs_idx], 0)
+                ss = align.scale_shift(cur_kf, old_kf)
+                new = align.depth_align(depth[P:P + 1], (fh, fw), ss=ss, clip=False)
+            for k in range(new.shape[0]):
+                kept[emitted] = new[k]
+                ring.push(new[k])
+                emitted += 1
+            for j in [j for j in kept if j != 0 and j < emitted - sch.n_slots]:
+                del kept[j]
+            continue
         d = io.resize_depth(depth, (fh, fw)).cpu().numpy()
         if not align_each_new_frame or not emitted_first:
             depth_list += [d[k] for k in range(d.shape[0])]
@@ -170,6 +246,8 @@ def infere_single_image(engine, frames, target_fps, input_size: int = 518, devic
         scale, shift = compute_scale_and_shift(np.concatenate(cur_kf), np.concatenate(old_kf),
                                                np.concatenate(np.ones_like(old_kf) == 1))
         depth_list.append(cur * scale + shift)
+    if on_device:
+        depth_list = ring.result()
     if align_each_new_frame:
         return np.stack(depth_list[1:n], axis=0), target_fps
     return np.stack(depth_list[:n], axis=0), target_fps

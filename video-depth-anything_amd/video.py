@@ -12,7 +12,9 @@ Mirrors ``VideoDepthAnything.infer_video_depth`` (video_depth.py:329-417) and it
   them over ranks (one process per GPU, RCCL) with no data-path collective but the final depth
   gather to rank 0;
 * rank 0 stitches: least-squares scale/shift on keyframe slots {0, 12}, 8-frame linear blend,
-  clip at 0 (:379-413).
+  clip at 0 (:379-413): on the host in the reference's numpy arithmetic (``Stitcher``, the default),
+  or with ``stitch="device"`` on the device (``DeviceStitcher`` on vda_scale_shift /
+  vda_depth_align), where the windows stay at network resolution until they are aligned.
 
 Preprocessing (bicubic resize + normalise) and the final depth resize run as libvda kernels
 (``DeviceIO``).  cv2 is not available here, so the bicubic resize is pinned against torch bicubic
@@ -101,6 +103,68 @@ class DeviceIO:
         return ops.depth_resize(depth.float().contiguous(), int(size[0]), int(size[1]))
 
 
+class DeviceAlign:
+    """The alignment arithmetic of the device stitcher (``stitch="device"``) on libvda kernels:
+    ``scale_shift(pred, target, mask=None)`` -> ss [2] fp32 on the device (least squares with fp64
+    sums, vda_scale_shift) and ``depth_align(src[F, H, W], size, ss=None, clip=True, pre=None,
+    w_pre=None, w_post=None, out=None)`` -> [F, h, w] (resize, ``* scale + shift``, clip at 0, blend
+    into ``pre``; vda_depth_align).  Neither reads a value back to the host.  The drivers take any
+    object with these two methods, as they take ``io=`` (``TorchAlign`` runs on any device)."""
+
+    @staticmethod
+    def scale_shift(pred: torch.Tensor, target: torch.Tensor, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+        from . import ops
+        return ops.scale_shift(pred, target, mask=mask)[0]
+
+    @staticmethod
+    def depth_align(src: torch.Tensor, size: tuple, ss=None, clip: bool = True, pre=None, w_pre=None, w_post=None,
+                    out=None) -> torch.Tensor:
+        from . import ops
+        return ops.depth_align(src.float().contiguous(), int(size[0]), int(size[1]), ss=ss, clip=clip, pre=pre,
+                               w_pre=w_pre, w_post=w_post, out=out)
+
+
+class TorchAlign:
+    """``DeviceAlign``'s contract in plain torch on any device: fp64 sums, ``F.interpolate(...,
+    align_corners=True)``, multiply and add as separate (separately rounded) ops.  It lets the device
+    stitcher's orchestration run on the CPU; it is not a fallback of the product path."""
+
+    @staticmethod
+    def scale_shift(pred: torch.Tensor, target: torch.Tensor, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+        p, t = pred.reshape(-1).double(), target.reshape(-1).double()
+        m = torch.ones_like(p) if mask is None else mask.reshape(-1).double()
+        a00, a01, a11 = (m * p * p).sum(), (m * p).sum(), m.sum()
+        b0, b1 = (m * p * t).sum(), (m * t).sum()
+        det = a00 * a11 - a01 * a01
+        ok = det != 0
+        den = torch.where(ok, det, torch.ones_like(det))
+        x0 = torch.where(ok, (a11 * b0 - a01 * b1) / den, torch.ones_like(det))
+        x1 = torch.where(ok, (-a01 * b0 + a00 * b1) / den, torch.zeros_like(det))
+        return torch.stack([x0, x1]).float()
+
+    @staticmethod
+    def depth_align(src: torch.Tensor, size: tuple, ss=None, clip: bool = True, pre=None, w_pre=None, w_post=None,
+                    out=None) -> torch.Tensor:
+        import torch.nn.functional as F
+        v = F.interpolate(src.float().unsqueeze(1), size=(int(size[0]), int(size[1])), mode="bilinear",
+                          align_corners=True)[:, 0]
+        if ss is not None:
+            v = v * ss[0]
+            v = v + ss[1]
+        if clip:
+            v = torch.where(v < 0, torch.zeros_like(v), v)
+        if pre is not None:
+            w0 = torch.tensor([float(x) for x in w_pre], dtype=torch.float32, device=v.device).view(-1, 1, 1)
+            w1 = torch.tensor([float(x) for x in w_post], dtype=torch.float32, device=v.device).view(-1, 1, 1)
+            a = pre * w0
+            b = v * w1
+            v = a + b
+        if out is None:
+            return v
+        out.copy_(v)
+        return out
+
+
 # ---- stitching (video_depth.py:375-413, utils/util.py:40-73) --------------------------------
 def compute_scale_and_shift(prediction, target, mask):
     prediction = prediction.astype(np.float32)
@@ -119,10 +183,15 @@ def compute_scale_and_shift(prediction, target, mask):
     return x_0, x_1
 
 
+def blend_weights(n: int) -> List[float]:
+    """get_interpolate_frames' weight of the post frame (utils/util.py:65-73), as Python floats."""
+    step = 1.0 / (n - 1)
+    return [0.0] + [i * step for i in range(1, n - 1)] + [1.0]
+
+
 def interpolate_frames(pre: Sequence[np.ndarray], post: Sequence[np.ndarray]) -> List[np.ndarray]:
     n = len(pre)
-    step = 1.0 / (n - 1)
-    w = [0.0] + [i * step for i in range(1, n - 1)] + [1.0]
+    w = blend_weights(n)
     return [pre[i] * (1 - w[i]) + post[i] * w[i] for i in range(n)]
 
 
@@ -188,7 +257,169 @@ def stitch(depth_list: List[np.ndarray], n_frames: int) -> np.ndarray:
     return st.result()
 
 
+class DeviceStitcher:
+    """``Stitcher`` restated on tensors that stay where the windows are (``stitch="device"``).  ``add``
+    takes each window at NETWORK resolution [32, H, W], in order, and returns the frames that have
+    settled as a tuple of [m, h, w] blocks; ``size`` = (h, w) is the output size (None: the windows'
+    own).  State: ``ref_align`` [2, h, w] and the INTERP_LEN still-blendable tail frames.  A window
+    k >= 1 costs two small launches (resize slots 0-1, their scale/shift against ``ref_align``) and two
+    passes that resize, align, clip and blend (slots 2-9 into the tail in place, slots 10-31); the
+    resized, unaligned window never exists in memory, no scalar is read back and nothing waits on the
+    host.  The scale/shift sums are fp64 here and fp32 on the host path."""
+
+    def __init__(self, n_frames: int, align=DeviceAlign, size: Optional[tuple] = None):
+        self.n = int(n_frames)
+        self.align = align
+        self.size = None if size is None else (int(size[0]), int(size[1]))
+        self.ref_align: Optional[torch.Tensor] = None
+        self.tail: Optional[torch.Tensor] = None
+        w = blend_weights(INTERP_LEN)  # the Python floats interpolate_frames multiplies float32 frames by
+        self.w_pre = [float(np.float32(1 - x)) for x in w]
+        self.w_post = [float(np.float32(x)) for x in w]
+
+    def state(self) -> tuple:
+        return tuple(t for t in (self.ref_align, self.tail) if t is not None)
+
+    def add(self, win: torch.Tensor) -> tuple:
+        size = self.size or (int(win.shape[-2]), int(win.shape[-1]))
+        align_len = OVERLAP - INTERP_LEN
+        kf_align = KEYFRAMES[:align_len]
+        al = self.align
+        if self.tail is None:
+            r = al.depth_align(win[:INFER_LEN], size, clip=False)
+            self.ref_align = torch.stack([r[kf] for kf in kf_align], 0)
+            self.tail = r[INFER_LEN - INTERP_LEN:]
+            return (r[:INFER_LEN - INTERP_LEN],)
+        cur = al.depth_align(win[:align_len], size, clip=False)
+        ss = al.scale_shift(cur, self.ref_align)
+        settled = al.depth_align(win[align_len:OVERLAP], size, ss=ss, clip=True, pre=self.tail, w_pre=self.w_pre,
+                                 w_post=self.w_post, out=self.tail)
+        new = al.depth_align(win[OVERLAP:INFER_LEN], size, ss=ss, clip=True)
+        for j, kf in enumerate(kf_align):
+            if j >= 1:  # slot 0's reference stays window 0's (video_depth.py:409-413)
+                self.ref_align[j].copy_(new[kf - OVERLAP])
+        self.tail = new[new.shape[0] - INTERP_LEN:]
+        return (settled, new[:new.shape[0] - INTERP_LEN])
+
+    def finish(self) -> tuple:
+        tail, self.tail = self.tail, None
+        return () if tail is None else (tail,)
+
+
 # ---- driver ---------------------------------------------------------------------------------
+class _DeviceSink:
+    """``_HostSink``'s contract (``put`` windows in any order, ``result`` raises on a missing one) for
+    ``stitch="device"``: the windows arrive at network resolution and are stitched where they are
+    (``DeviceStitcher``).  The settled frames go either into a preallocated device [n, h, w] tensor
+    (``return_device``) or to the host through a ring of two pinned staging buffers with non-blocking
+    copies, 22 frames per window (the host path moves all 32), so device memory stays flat in the
+    video length.  Windows may be put under different streams: a step waits for the event of the
+    previous one, and every buffer that outlives a step is ``record_stream``-ed on the stream that
+    uses it (the discipline ``land`` in ``infer_video_depth`` documents for side-stream buffers)."""
+
+    def __init__(self, device: torch.device, n_frames: int, size: Optional[tuple] = None, align=DeviceAlign,
+                 return_device: bool = False):
+        self.dev = device
+        self.gpu = device.type == "cuda"
+        self.n = int(n_frames)
+        self.return_device = bool(return_device)
+        self.stitcher = DeviceStitcher(n_frames, align, size)
+        self.ready = {}          # window id -> (window, event or None): landed, not yet stitchable
+        self.next = 0
+        self.done = 0
+        self.out: Optional[torch.Tensor] = None    # device result (return_device, or a CPU run)
+        self.host: Optional[np.ndarray] = None     # host result (GPU run with host output)
+        self.ring: list = []
+        self.pending: list = []  # (first frame, frame count, staging slot, event)
+        self.last = None         # event after the latest stitch step
+
+    def _drain(self, keep: int):
+        while len(self.pending) > keep:
+            pos, m, slot, ev = self.pending.pop(0)
+            ev.synchronize()
+            self.host[pos:pos + m] = slot[:m].numpy()
+
+    def _emit(self, blocks: Sequence[torch.Tensor]):
+        m = min(sum(int(b.shape[0]) for b in blocks), self.n - self.done)
+        if m <= 0:
+            return
+        shape = tuple(blocks[0].shape[1:])
+        if self.return_device or not self.gpu:
+            if self.out is None:
+                self.out = torch.empty((self.n,) + shape, dtype=torch.float32, device=self.dev)
+            dst = self.out[self.done:self.done + m]
+            if self.gpu:
+                self.out.record_stream(torch.cuda.current_stream(self.dev))
+        else:
+            if self.host is None:
+                self.host = np.empty((self.n,) + shape, dtype=np.float32)
+            self._drain(1)
+            busy = {id(s) for _, _, s, _ in self.pending}
+            cap = (INFER_LEN - INTERP_LEN,) + shape
+            dst = next((s for s in self.ring if id(s) not in busy and tuple(s.shape) == cap), None)
+            if dst is None:
+                dst = torch.empty(cap, dtype=torch.float32, pin_memory=True)
+                self.ring.append(dst)
+                self.ring = self.ring[-2:]
+        at = 0
+        for b in blocks:
+            c = min(int(b.shape[0]), m - at)
+            if c > 0:
+                dst[at:at + c].copy_(b[:c], non_blocking=True)
+            at += c
+        if self.gpu and not self.return_device:
+            ev = torch.cuda.Event()
+            ev.record()
+            self.pending.append((self.done, m, dst, ev))
+        self.done += m
+
+    def _on_current_stream(self, extra=()):
+        """Order the current stream behind the previous stitch step and tell the caching allocator that
+        it uses the buffers that step left (they may have been allocated under another stream)."""
+        if not self.gpu:
+            return
+        cur = torch.cuda.current_stream(self.dev)
+        if self.last is not None:
+            cur.wait_event(self.last)
+        for t in self.stitcher.state() + tuple(extra):
+            if t.is_cuda:
+                t.record_stream(cur)
+
+    def _stitch(self, d: torch.Tensor, ev):
+        if self.gpu and ev is not None:
+            torch.cuda.current_stream(self.dev).wait_event(ev)
+        self._on_current_stream((d,))
+        self._emit(self.stitcher.add(d))
+        if self.gpu:
+            self.last = torch.cuda.Event()
+            self.last.record()
+
+    def put(self, k: int, d: torch.Tensor):
+        d = d.detach()
+        if d.dtype != torch.float32 or not d.is_contiguous():
+            d = d.float().contiguous()
+        ev = None
+        if self.gpu:
+            ev = torch.cuda.Event()
+            ev.record()  # d is complete once the stream it was produced (or received) on reaches this
+        self.ready[k] = (d, ev)
+        while self.next in self.ready:
+            self._stitch(*self.ready.pop(self.next))
+            self.next += 1
+
+    def result(self):
+        if self.ready:
+            raise RuntimeError(f"windows {sorted(self.ready)} never became stitchable (missing {self.next})")
+        self._on_current_stream()
+        self._emit(self.stitcher.finish())
+        if self.return_device:
+            return self.out[:self.done]
+        if not self.gpu:
+            return self.out[:self.done].numpy()
+        self._drain(0)
+        return self.host[:self.done]
+
+
 class _HostSink:
     """Moves each window's resized depth [32, h, w] off the device as soon as it exists (as the
     reference does, video_depth.py:372-373), so device memory stays flat in the video length, and
@@ -286,7 +517,8 @@ def _gather_round(buf: torch.Tensor, rank: int, world: int, group):
 
 def infer_video_depth(forward: Callable[[torch.Tensor], torch.Tensor], frames, target_fps, input_size: int = 518,
                       device="cuda", windows_per_batch: int = 1, rank: int = 0, world: int = 1, group=None,
-                      io=DeviceIO, streams: int = 2, prepare: Optional[Callable[[tuple], None]] = None):
+                      io=DeviceIO, streams: int = 2, prepare: Optional[Callable[[tuple], None]] = None,
+                      stitch: str = "host", return_device: bool = False, align=DeviceAlign):
     """Depth for every frame of ``frames`` (uint8 [N, h, w, 3] numpy or tensor).
 
     ``forward(x[B, 32, 3, H, W]) -> depth[B, 32, H, W]`` is the clip forward (the model, or any
@@ -303,7 +535,17 @@ def infer_video_depth(forward: Callable[[torch.Tensor], torch.Tensor], frames, t
     one window's forward can start while the previous one's tail kernels run (one GPU, two streams:
     the 176-frame ViT-L job in 414-420 ms against 442 ms on one stream and 413 ms for its 8 forwards
     back to back; ``tools/archive/video_probe.py``).  Each rank of a multi-GPU job does the same.
+
+    ``stitch="device"`` keeps the windows on the device: the per-window ``io.resize_depth`` is skipped,
+    the multi-rank gather carries network-resolution windows, and rank 0 resizes while it aligns
+    (``DeviceStitcher`` on the ``align`` backend; fp64 scale/shift sums where the host path sums in
+    fp32, so the two modes agree to the fp32 tier, not bit for bit).  ``return_device=True`` (device
+    mode only) returns the depth as a [N, h, w] fp32 tensor on ``device`` instead of a numpy array.
     """
+    if stitch not in ("host", "device"):
+        raise ValueError(f"stitch must be 'host' or 'device', got {stitch!r}")
+    if return_device and stitch != "device":
+        raise ValueError("return_device=True needs stitch='device' (the host stitcher returns numpy)")
     if not isinstance(frames, torch.Tensor):
         frames = torch.from_numpy(np.ascontiguousarray(frames))
     n = frames.shape[0]
@@ -312,7 +554,11 @@ def infer_video_depth(forward: Callable[[torch.Tensor], torch.Tensor], frames, t
     nwin = len(window_starts(n))
     rounds = (nwin + world - 1) // world
     dev = torch.device(device)
-    sink = _HostSink(dev, n) if rank == 0 else None
+    on_device = stitch == "device"
+    out_hw = size if on_device else (h, w)  # the size a window has when it reaches the sink / the gather
+    sink = None
+    if rank == 0:
+        sink = _DeviceSink(dev, n, (h, w), align, return_device) if on_device else _HostSink(dev, n)
     source = _HostSource(frames, dev)
     wpb = max(1, int(windows_per_batch))
     if prepare is None and callable(getattr(forward, "prepare", None)):  # the model itself as the forward
@@ -359,14 +605,17 @@ def infer_video_depth(forward: Callable[[torch.Tensor], torch.Tensor], frames, t
                 with torch.no_grad():
                     d = forward(x).float()  # [B, 32, H, W]
                 del x
-                d = io.resize_depth(d.flatten(0, 1), (h, w)).view(len(ks), INFER_LEN, h, w)
+                if on_device:
+                    d = d.contiguous()
+                else:
+                    d = io.resize_depth(d.flatten(0, 1), (h, w)).view(len(ks), INFER_LEN, h, w)
             if world == 1:
                 for j, k in enumerate(ks):
                     sink.put(k, d[j])
                 continue
             # every rank takes part in every round's gather (a rank without a window sends zeros),
             # enqueued behind this round's forward on its stream
-            buf = torch.zeros(len(rr), INFER_LEN, h, w, dtype=torch.float32, device=dev)
+            buf = torch.zeros(len(rr), INFER_LEN, out_hw[0], out_hw[1], dtype=torch.float32, device=dev)
             if d is not None:
                 buf[:len(ks)] = d
             cur = _gather_round(buf, rank, world, group) + (rr,)
