@@ -307,6 +307,53 @@ int vda_depth_align(const float* src, int32_t F, int32_t H, int32_t W, int32_t h
                     void* stream);
 
 /*
+ * Ground-truth evaluation on the device (the reference's eval.py:149-181): pred [F, S] float is the model's
+ * relative inverse depth, gt [F, S] float metres, valid [F, S] uint8 (non-zero = valid, NULL = all valid),
+ * S = h * w elements per frame, frames at f * S.  Both entry points are streaming reductions in the manner of
+ * vda_scale_shift: every per-pixel operation is one correctly rounded fp32 operation (-, /, *, compare,
+ * select; no reciprocal approximation, no contraction), every sum is fp64 in a fixed order (per thread ->
+ * wave -> block -> a frame's block partials in index order -> frames in frame order), so the same input
+ * gives the same bits on every run, and frame f of an [F, S] call gets the bits of a single-frame call on
+ * it.  Invalid pixels are selected out, not multiplied out: gt may be 0 or NaN there and reaches no sum.
+ * No atomics, no allocation, no synchronisation; the results stay on the device.  1 <= F <= 65535 (the
+ * launch grid), S >= 1, pred / gt / ss / aligned 4-byte aligned, the double arrays and ws 8-byte aligned.
+ * ws: vda_depth_eval_workspace(F, S) bytes of device memory owned by the caller; it needs no
+ * initialisation and holds nothing between calls.
+ *
+ * vda_depth_eval_fit: G = per_frame ? F : 1 least-squares fits in inverse depth over the valid pixels,
+ *   minimise S (c0 pred + c1 - t)^2, t = 1 / gt (an fp32 division), from
+ *   sums [G, 5] double (may be NULL) = (S p^2, S p, S 1, S p t, S t), det = a_00 a_11 - a_01^2,
+ *   c0 = (a_11 b_0 - a_01 b_1) / det, c1 = (-a_01 b_0 + a_00 b_1) / det in fp64, and
+ *   ss [G, 2] float = (scale, shift) = (1 / c0, -c1 / c0), rounded to fp32 once, on the store.
+ *   Replaces align_prediction's fit (utils/align.py:192-207 -> frame_aligning_scale_shift_lstsq, :151-160),
+ *   which gathers the valid pixels into an [n_valid, 2] matrix on the host for an SVD lstsq.
+ *   Deviation: with no valid pixel, det == 0 (e.g. a constant pred) or c0 == 0 the result is (inf, 0), and
+ *   every aligned pixel becomes max_depth; the reference does this for c0 == 0 only, its lstsq returns a
+ *   minimum-norm solution in the other two cases.
+ *
+ * vda_depth_eval_metrics: with (scale, shift) = ss[ss_per_frame ? f : 0], per pixel in fp32
+ *   a = clip((pred - shift) / scale, 0, 1);  a = a == 0 ? 1e-4f : a;  p = clip(1 / a, 0, max_depth)
+ *   (utils/align.py:210-216; clip lets NaN through as numpy's does), and over the valid pixels with
+ *   g = gt, d = p - g:
+ *   frame_sums [F, 8] double = (count, #{max(p/g, g/p) > 1.25}, #{.. > 1.5625}, #{.. > 1.953125},
+ *                               S d/g, S |d|, S |d|/g, S d*d)      (the terms are fp32, the sums fp64)
+ *   total [8] double (may be NULL) = frame_sums added in frame order;
+ *   aligned [F, S] float (may be NULL) = p of every pixel, valid or not.  max_depth > 0.
+ *   Delta_k = 1 - sums[k] / count, SignedRelative = sums[4] / count, AbsoluteError = sums[5] / count,
+ *   AbsoluteRelative = sums[6] / count, MeanSquaredError = sums[7] / count: utils/metrics.py:24-31, :91-192,
+ *   ten full-size host passes in the reference.
+ *   Deviation: under numpy >= 2 the reference's scale is a float64 scalar, which promotes its aligned map
+ *   and every metric to float64; under numpy 1.x the same code stays in float32.  Here the per-pixel
+ *   arithmetic is fp32 always, so `aligned` equals the separate torch fp32 ops bit for bit.
+ */
+int64_t vda_depth_eval_workspace(int32_t F, int64_t S);
+int vda_depth_eval_fit(const float* pred, const float* gt, const uint8_t* valid, int32_t F, int64_t S,
+                       int32_t per_frame, double* sums, float* ss, void* ws, int64_t ws_bytes, void* stream);
+int vda_depth_eval_metrics(const float* pred, const float* gt, const uint8_t* valid, int32_t F, int64_t S,
+                           const float* ss, int32_t ss_per_frame, float max_depth, float* aligned,
+                           double* frame_sums, double* total, void* ws, int64_t ws_bytes, void* stream);
+
+/*
  * fp32 mode (infer_video_depth(fp32=True) / autocast off, video_depth.py:366-368): the same ops
  * with fp32 activations AND fp32 weights, fp32 accumulation on the exact-f32 MFMA
  * (v_mfma_f32_16x16x4_f32), exact-erf GELU, expf softmax.  Same layouts and epilogue contract as

@@ -24,11 +24,10 @@ REPO = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, REPO)
 
 
-def parse(argv=None):
-    p = argparse.ArgumentParser(description="Video Depth Anything (MI355X)")
+def add_model_arguments(p):
+    """The model, input and inference flags (eval.py takes the same ones)."""
     p.add_argument("--device", type=str, default="cuda:0")
     p.add_argument("--input_video", type=str, required=True)
-    p.add_argument("--output_dir", type=str, default="./outputs")
     p.add_argument("--process_single_image", action="store_true")
     p.add_argument("--inference_length", type=int, default=32)
     p.add_argument("--keyframe_list", type=int, nargs="+", default=[20])
@@ -41,6 +40,17 @@ def parse(argv=None):
     p.add_argument("--max_len", type=int, default=-1)
     p.add_argument("--target_fps", type=int, default=-1)
     p.add_argument("--fp32", action="store_true")
+    p.add_argument("--checkpoint", type=str, default=None)
+    p.add_argument("--synthetic_weights", action="store_true")
+    p.add_argument("--windows_per_batch", type=int, default=1,
+                   help="windows per forward in the long-video path (2: ~3%% more frames/s on MI355X)")
+    return p
+
+
+def add_arguments(p):
+    """Every flag of this tool: the model / inference flags and the output flags."""
+    add_model_arguments(p)
+    p.add_argument("--output_dir", type=str, default="./outputs")
     p.add_argument("--grayscale", action="store_true")
     p.add_argument("--save_npz", action="store_true")
     p.add_argument("--save_tiff", action="store_true")
@@ -48,31 +58,39 @@ def parse(argv=None):
     p.add_argument("--save_vis", action="store_true")
     p.add_argument("--save_stats", action="store_true")
     p.add_argument("--vis_format", type=str, default="y4m", choices=["y4m", "gif", "png", "webp", "mp4"])
-    p.add_argument("--checkpoint", type=str, default=None)
-    p.add_argument("--synthetic_weights", action="store_true")
-    p.add_argument("--windows_per_batch", type=int, default=1,
-                   help="windows per forward in the long-video path (2: ~3%% more frames/s on MI355X)")
     p.add_argument("--stitch", type=str, default="host", choices=["host", "device"],
                    help="where windows (or, with --process_single_image --align_each_new_frame, new frames) are "
                         "aligned and stitched: on the host as the reference does, or on the device")
-    a = p.parse_args(argv)
+    return p
+
+
+def check_args(a):
     assert a.inference_length > len(a.keyframe_list) + 2, "Inference length to small for the number of geiven keyframes"
     return a
 
 
-def main(argv=None):
-    args = parse(argv)
+def parse(argv=None):
+    p = add_arguments(argparse.ArgumentParser(description="Video Depth Anything (MI355X)"))
+    return check_args(p.parse_args(argv))
+
+
+def load_model(args):
+    """The model of ``--encoder`` on ``--device``: the checkpoint, or the synthetic recipe weights."""
     import vda_amd
-    from vda_amd import video_io as VIO
     if not torch.cuda.is_available():
         raise RuntimeError("the MI355X path needs a GPU (there is no CPU mode)")
-    dev = args.device
     if args.synthetic_weights:
-        model = vda_amd.build_model(args.encoder, device=dev)
-    else:
-        ck = args.checkpoint or os.path.join("checkpoints", f"video_depth_anything_{args.encoder}.pth")
-        sd = torch.load(ck, map_location="cpu", weights_only=True)
-        model = vda_amd.build_model(args.encoder, state_dict=sd, device=dev)
+        return vda_amd.build_model(args.encoder, device=args.device)
+    ck = args.checkpoint or os.path.join("checkpoints", f"video_depth_anything_{args.encoder}.pth")
+    sd = torch.load(ck, map_location="cpu", weights_only=True)
+    return vda_amd.build_model(args.encoder, state_dict=sd, device=args.device)
+
+
+def main(argv=None):
+    args = parse(argv)
+    from vda_amd import video_io as VIO
+    model = load_model(args)
+    dev = args.device
     if args.save_stats:
         torch.cuda.reset_peak_memory_stats(dev)
     frames, target_fps = VIO.read_video_frames(args.input_video, args.max_len, args.target_fps, args.max_res)

@@ -27,6 +27,7 @@ EXPORTED = (
     "vda_spatial_attention", "vda_temporal_attention", "vda_upsample_bilinear", "vda_patch_im2col",
     "vda_depth_head", "vda_depth_head_workspace", "vda_preprocess_frames", "vda_depth_resize",
     "vda_scale_shift", "vda_scale_shift_workspace", "vda_depth_align",
+    "vda_depth_eval_workspace", "vda_depth_eval_fit", "vda_depth_eval_metrics",
     "vda_gemm_f32", "vda_conv2d_f32", "vda_layernorm_f32", "vda_groupnorm_f32", "vda_spatial_attention_f32",
     "vda_temporal_attention_f32", "vda_upsample_bilinear_f32", "vda_patch_im2col_f32", "vda_depth_head_f32",
 )
@@ -93,6 +94,9 @@ def _declare(lib):
         "vda_scale_shift_workspace": ([L], L),
         "vda_scale_shift": ([P, P, P, L, P, P, P, L, P], I),
         "vda_depth_align": ([P, I, I, I, I, I, P, I, P, POINTER(F), POINTER(F), P, P], I),
+        "vda_depth_eval_workspace": ([I, L], L),
+        "vda_depth_eval_fit": ([P, P, P, I, L, I, P, P, P, L, P], I),
+        "vda_depth_eval_metrics": ([P, P, P, I, L, P, I, F, P, P, P, P, L, P], I),
         "vda_gemm_f32": ([P, L, P, P, L, I, I, I, EP, P], I),
         "vda_conv2d_f32": ([P, P, P, I, I, I, I, I, I, I, I, I, EP, P], I),
         "vda_layernorm_f32": ([P, L, P, P, P, I, I, F, I, P], I),

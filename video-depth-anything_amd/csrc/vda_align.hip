@@ -20,11 +20,6 @@ constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / 64;
 constexpr int64_t kElemsPerBlock = (int64_t)kBlock * 4;  // one 16-byte load per thread and iteration
 
-// 16-byte groups of floats / 4-byte groups of mask bytes whose address is only element-aligned: target
-// and mask share pred's head, so their body loads start wherever that leaves them
-typedef float f4a4 __attribute__((ext_vector_type(4), aligned(4)));
-typedef uint8_t u8x4a1 __attribute__((ext_vector_type(4), aligned(1)));
-
 struct Sums {
   double v[5];  // a_00 = S m p^2, a_01 = S m p, a_11 = S m, b_0 = S m p t, b_1 = S m t
 };
@@ -37,12 +32,6 @@ __device__ __forceinline__ void accumulate(Sums& s, float p, float t, float m) {
   s.v[2] += dm;
   s.v[3] = fma(mp, dt, s.v[3]);
   s.v[4] = fma(dm, dt, s.v[4]);
-}
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 int scale_shift_grid(int64_t n) {

@@ -17,6 +17,11 @@ typedef short s4 __attribute__((ext_vector_type(4)));
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef float f16x __attribute__((ext_vector_type(16)));
+// 16-byte groups of floats / 4-byte groups of mask bytes whose address is only element-aligned: in the
+// streaming reductions (vda_align.hip, vda_eval.hip) the other operands share pred's head, so their
+// body loads start wherever that leaves them
+typedef float f4a4 __attribute__((ext_vector_type(4), aligned(4)));
+typedef uint8_t u8x4a1 __attribute__((ext_vector_type(4), aligned(1)));
 
 #define VDA_LDS __attribute__((address_space(3)))
 
@@ -133,6 +138,11 @@ __device__ __forceinline__ float gelu_erf(float x) {
 }
 
 __device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ double wave_sum_f64(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;

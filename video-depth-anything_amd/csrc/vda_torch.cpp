@@ -564,6 +564,64 @@ Tensor depth_align(const Tensor& src, int64_t ho, int64_t wo, OptT ss, bool clip
   return out;
 }
 
+// ---- ground-truth evaluation -------------------------------------------------------------------
+// pred / gt [F, ...] float and valid [F, ...] uint8 with the same number of elements per frame.
+int64_t eval_inputs(const char* op, const Tensor& pred, const Tensor& gt, OptT valid) {
+  TORCH_CHECK(pred.scalar_type() == at::kFloat && pred.is_contiguous() && pred.dim() >= 1 && pred.numel() >= 1,
+              "vda ", op, ": pred must be a contiguous, non-empty float [F, ...] tensor");
+  TORCH_CHECK(pred.size(0) <= 65535, "vda ", op, ": F <= 65535 frames per call, got ", pred.size(0));
+  need_contig(gt, at::kFloat, "gt", pred);
+  TORCH_CHECK(gt.sizes() == pred.sizes(), "vda ", op, ": gt must have pred's shape");
+  if (valid) {
+    need_contig(*valid, at::kByte, "valid", pred);
+    TORCH_CHECK(valid->sizes() == pred.sizes(), "vda ", op, ": valid must have pred's shape");
+  }
+  return pred.numel() / pred.size(0);
+}
+
+std::tuple<Tensor, Tensor> depth_eval_fit(const Tensor& pred, const Tensor& gt, OptT valid, bool per_frame) {
+  const int64_t S = eval_inputs("depth_eval_fit", pred, gt, valid);
+  const int64_t F = pred.size(0), G = per_frame ? F : 1;
+  Tensor ss = at::empty({G, 2}, pred.options());
+  Tensor sums = at::empty({G, 5}, pred.options().dtype(at::kDouble));
+  if (pred.is_meta()) return {ss, sums};
+  const at::OptionalDeviceGuard g(pred.device());
+  const int64_t wsb = vda_depth_eval_workspace((int32_t)F, S);
+  Tensor ws = at::empty({wsb}, pred.options().dtype(at::kByte));
+  check_rc(vda_depth_eval_fit((const float*)pred.data_ptr(), (const float*)gt.data_ptr(), (const uint8_t*)ptr(valid),
+                              (int32_t)F, S, per_frame ? 1 : 0, (double*)sums.data_ptr(), (float*)ss.data_ptr(),
+                              ws.data_ptr(), wsb, stream_of(pred)),
+           "vda_depth_eval_fit");
+  return {ss, sums};
+}
+
+std::tuple<Tensor, Tensor, optional<Tensor>> depth_eval_metrics(const Tensor& pred, const Tensor& gt, OptT valid,
+                                                                const Tensor& ss, double max_depth,
+                                                                bool want_aligned) {
+  const int64_t S = eval_inputs("depth_eval_metrics", pred, gt, valid);
+  const int64_t F = pred.size(0);
+  need_contig(ss, at::kFloat, "ss", pred);
+  TORCH_CHECK(ss.numel() == 2 || (ss.numel() == 2 * F && ss.dim() == 2),
+              "vda depth_eval_metrics: ss must hold (scale, shift) once ([2] or [1, 2]) or per frame ([F, 2])");
+  TORCH_CHECK(max_depth > 0., "vda depth_eval_metrics: max_depth must be greater than 0");
+  const bool ss_per_frame = ss.dim() == 2 && ss.size(0) == F && F > 1;
+  Tensor frame_sums = at::empty({F, 8}, pred.options().dtype(at::kDouble));
+  Tensor total = at::empty({8}, pred.options().dtype(at::kDouble));
+  optional<Tensor> aligned;
+  if (want_aligned) aligned = at::empty(pred.sizes(), pred.options());
+  if (pred.is_meta()) return {frame_sums, total, aligned};
+  const at::OptionalDeviceGuard g(pred.device());
+  const int64_t wsb = vda_depth_eval_workspace((int32_t)F, S);
+  Tensor ws = at::empty({wsb}, pred.options().dtype(at::kByte));
+  check_rc(vda_depth_eval_metrics((const float*)pred.data_ptr(), (const float*)gt.data_ptr(),
+                                  (const uint8_t*)ptr(valid), (int32_t)F, S, (const float*)ss.data_ptr(),
+                                  ss_per_frame ? 1 : 0, (float)max_depth, aligned ? (float*)aligned->data_ptr() : nullptr,
+                                  (double*)frame_sums.data_ptr(), (double*)total.data_ptr(), ws.data_ptr(), wsb,
+                                  stream_of(pred)),
+           "vda_depth_eval_metrics");
+  return {frame_sums, total, aligned};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(vda, m) {
@@ -593,6 +651,9 @@ TORCH_LIBRARY(vda, m) {
   m.def("scale_shift(Tensor pred, Tensor target, Tensor? mask=None) -> (Tensor ss, Tensor sums)");
   m.def("depth_align(Tensor src, int ho, int wo, Tensor? ss=None, bool clip=True, Tensor? pre=None, "
         "float[]? w_pre=None, float[]? w_post=None, Tensor(a!)? out=None) -> Tensor");
+  m.def("depth_eval_fit(Tensor pred, Tensor gt, Tensor? valid=None, bool per_frame=False) -> (Tensor ss, Tensor sums)");
+  m.def("depth_eval_metrics(Tensor pred, Tensor gt, Tensor? valid, Tensor ss, float max_depth=80., "
+        "bool want_aligned=False) -> (Tensor frame_sums, Tensor total, Tensor? aligned)");
 }
 
 #define VDA_IMPL(KEY)                                         \
@@ -614,6 +675,8 @@ TORCH_LIBRARY(vda, m) {
     m.impl("depth_resize", &depth_resize);                    \
     m.impl("scale_shift", &scale_shift);                      \
     m.impl("depth_align", &depth_align);                      \
+    m.impl("depth_eval_fit", &depth_eval_fit);                \
+    m.impl("depth_eval_metrics", &depth_eval_metrics);        \
   }
 
 VDA_IMPL(CUDA)

@@ -798,6 +798,17 @@ def _infer_video_depth(self, frames, target_fps, input_size=518, device="cuda", 
 VideoDepthAnything.infer_video_depth = _infer_video_depth
 
 
+def _evaluate_video_depth(self, frames, target_fps, gt, valid=None, *, max_depth=80., align="all", **infer_kwargs):
+    """eval.py:119-181 on the device: ``infer_video_depth(..., stitch="device", return_device=True)`` (with
+    ``streaming=True`` ``infere_single_image``), then the inverse-depth fit and the seven metrics against
+    ``gt`` / ``valid`` on the stitched device tensor (see vda_amd.evaluate) -> (EvalResult, fps)."""
+    from .evaluate import evaluate_video_depth
+    return evaluate_video_depth(self, frames, target_fps, gt, valid, max_depth=max_depth, align=align, **infer_kwargs)
+
+
+VideoDepthAnything.evaluate_video_depth = _evaluate_video_depth
+
+
 def build_model(encoder: str = "vitl", state_dict: Optional[dict] = None, device="cuda",
                 pe: str = "ape", use_bn: bool = False, use_clstoken: bool = False) -> VideoDepthAnything:
     """Construct, load weights (reference checkpoint dict or the synthetic recipe), move to device."""

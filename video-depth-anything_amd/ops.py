@@ -235,3 +235,51 @@ def depth_align(src: Tensor, ho: int, wo: int, *, ss: Optional[Tensor] = None, c
     if out is not None:
         _need(out, torch.float32, "out")
     return _vda().depth_align(src, int(ho), int(wo), ss, bool(clip), pre, w_pre, w_post, out)
+
+
+def _eval_inputs(pred: Tensor, gt: Tensor, valid: Optional[Tensor]):
+    """Checks shared by the evaluation ops; returns ``valid`` as uint8 (a bool mask is viewed, not copied)."""
+    for name, t in (("pred", pred), ("gt", gt)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
+            raise ValueError(f"{name} must be a float32 GPU tensor (no CPU path in the product)")
+    if pred.dim() < 1 or pred.numel() < 1 or not 1 <= pred.shape[0] <= 65535:
+        raise ValueError(f"pred must be a non-empty [F, ...] tensor with 1 <= F <= 65535, got {tuple(pred.shape)}")
+    if gt.shape != pred.shape or gt.device != pred.device:
+        raise ValueError(f"gt must have pred's shape and device, got {tuple(gt.shape)} on {gt.device}")
+    if not pred.is_contiguous() or not gt.is_contiguous():
+        raise ValueError("pred and gt must be contiguous")
+    if valid is not None:
+        if not isinstance(valid, torch.Tensor) or valid.dtype not in (torch.bool, torch.uint8):
+            raise ValueError("valid must be a bool or uint8 tensor")
+        if valid.shape != pred.shape or valid.device != pred.device or not valid.is_contiguous():
+            raise ValueError(f"valid must be contiguous with pred's shape and device, got {tuple(valid.shape)} on {valid.device}")
+        if valid.dtype == torch.bool:
+            valid = valid.view(torch.uint8)
+    return valid
+
+
+def depth_eval_fit(pred: Tensor, gt: Tensor, valid: Optional[Tensor] = None, *, per_frame: bool = False):
+    """Masked least squares in inverse depth (the fit of the reference's ``align_prediction``): pred / gt
+    [F, ...] fp32 on the GPU, ``valid`` bool / uint8 of the same shape or None (all valid) -> (ss [G, 2] fp32
+    = (scale, shift), sums [G, 5] fp64), G = F with ``per_frame`` and 1 otherwise, both on the device.  A fit
+    without a solution gives (inf, 0).  fp64 sums in a fixed order, no host sync (vda.h vda_depth_eval_fit)."""
+    valid = _eval_inputs(pred, gt, valid)
+    return _vda().depth_eval_fit(pred, gt, valid, bool(per_frame))
+
+
+def depth_eval_metrics(pred: Tensor, gt: Tensor, valid: Optional[Tensor], ss: Tensor, *, max_depth: float = 80.,
+                       want_aligned: bool = False):
+    """Align with ``ss`` ([2] / [1, 2], or [F, 2] per frame; fp32 on the device), clip, invert and clip at
+    ``max_depth`` as ``align_prediction`` does, and sum the metric terms over the valid pixels in the same
+    pass -> (frame_sums [F, 8] fp64, total [8] fp64, aligned metric depth with pred's shape or None).  The
+    sums: count, outliers at 1.25 / 1.25^2 / 1.25^3, S d/g, S |d|, S |d|/g, S d^2
+    (vda.h vda_depth_eval_metrics)."""
+    valid = _eval_inputs(pred, gt, valid)
+    if not isinstance(ss, torch.Tensor) or ss.dtype != torch.float32 or ss.device != pred.device:
+        raise ValueError("ss must be a float32 tensor on pred's device")
+    F = pred.shape[0]
+    if not (ss.numel() == 2 or tuple(ss.shape) == (F, 2)) or not ss.is_contiguous():
+        raise ValueError(f"ss must be contiguous [2], [1, 2] or [F, 2] = (scale, shift), got {tuple(ss.shape)}")
+    if not float(max_depth) > 0.:
+        raise ValueError(f"max_depth must be greater than 0, got {max_depth}")
+    return _vda().depth_eval_metrics(pred, gt, valid, ss, float(max_depth), bool(want_aligned))
