@@ -360,6 +360,15 @@ int vda_depth_eval_metrics(const float* pred, const float* gt, const uint8_t* va
  * the fp16 entry points above (vda_epilogue.res / res2 are float here).  Parity tier (i) of
  * SURVEY.md §8(d).  Requirements: K, ldx, N multiples of 4 (GEGLU: N % 32 == 0); conv Cin, Cout
  * multiples of 4; spatial attention D == 64; temporal attention T <= 32, D <= 128.
+ * vda_gemm_f32 and vda_conv2d_f32 return -22 before any launch for what their kernel does not
+ * implement or cannot address (every row access is a float4):
+ *   ldx < K; ldy, ldres or ldres2 not a multiple of 4 (res / res2 rows may be strided otherwise);
+ *   drop_period != 0 (vda_gemm only: the fp32 kernel stores all M rows);
+ *   ln_stats, stats_out, res2_h / res2_w (fp16 entry points only);
+ *   a rowbias with rdiv <= 0 or rmod <= 0;
+ *   GEMM: VDA_ACT_GEGLU together with a rowbias, a res2 or the pixel-shuffle store (as vda_gemm);
+ *   conv: VDA_ACT_GEGLU, the pixel-shuffle store.
+ * sched is ignored (no persistent fp32 kernel).
  */
 int vda_gemm_f32(const float* x, int64_t ldx, const float* w, float* y, int64_t ldy,
                  int32_t M, int32_t N, int32_t K, const vda_epilogue* epi, void* stream);

@@ -111,6 +111,64 @@ def test_epilogue_combinations_rejected():
     assert lib.vda_gemm_f32(fake, 64, fake, fake, 256, 4096, 256, 64, e, None) == -22
 
 
+def _rejected(rc, msg):
+    assert rc == -22
+    err = _lib.lib().vda_last_error()
+    assert msg in err, err
+
+
+def test_gemm_f32_rejects_what_its_kernel_ignores():
+    """vda_gemm_f32 has one kernel: it stores all M rows, its GEGLU branch applies bias / gamma / res only,
+    and every row access is a float4.  What that kernel would ignore or mis-address is refused before
+    any launch (fake pointers: a launch would fault), each with its own message."""
+    lib = _lib.lib()
+    fake = ctypes.c_void_p(0x1000)
+    E = lambda **kw: _lib.Epilogue(rdiv=1, rmod=1, **kw)  # noqa: E731
+    # M, N, K = 4096, 256, 64 with ldx = 64, ldy = 256 is accepted up to the launch: vary one thing at a time
+    _rejected(lib.vda_gemm_f32(fake, 64, fake, fake, 256, 4096, 256, 64, E(drop_period=300), None), b"drop_period")
+    _rejected(lib.vda_gemm_f32(fake, 64, fake, fake, 256, 4096, 256, 64, E(drop_period=-1), None), b"drop_period")
+    geglu = _lib.ACT_GEGLU
+    _rejected(lib.vda_gemm_f32(fake, 64, fake, fake, 128, 4096, 256, 64, E(act=geglu, rowbias=0x2000), None),
+              b"no rowbias/res2, row store")
+    _rejected(lib.vda_gemm_f32(fake, 64, fake, fake, 128, 4096, 256, 64, E(act=geglu, res2=0x2000, ldres2=128), None),
+              b"no rowbias/res2, row store")
+    ps = dict(store=_lib.STORE_PIXEL_SHUFFLE, ps_k=2, ps_cout=64, ps_hin=64, ps_win=64)
+    _rejected(lib.vda_gemm_f32(fake, 64, fake, fake, 256, 4096, 256, 64, E(act=geglu, **ps), None),
+              b"no rowbias/res2, row store")
+    _rejected(lib.vda_gemm_f32(fake, 64, fake, fake, 128, 4096, 240, 64, E(act=geglu), None), b"N % 32")
+    _rejected(lib.vda_gemm_f32(fake, 64, fake, fake, 258, 4096, 256, 64, E(), None), b"ldy a multiple of 4")
+    _rejected(lib.vda_gemm_f32(fake, 64, fake, fake, 256, 4096, 256, 64, E(res=0x2000, ldres=258), None),
+              b"ldres a multiple of 4")
+    _rejected(lib.vda_gemm_f32(fake, 64, fake, fake, 256, 4096, 256, 64, E(res2=0x2000, ldres2=258), None),
+              b"ldres2 a multiple of 4")
+    _rejected(lib.vda_gemm_f32(fake, 60, fake, fake, 256, 4096, 256, 64, E(), None), b"ldx >= K")
+    _rejected(lib.vda_gemm_f32(fake, 62, fake, fake, 256, 4096, 256, 64, E(), None), b"multiples of 4")
+    _rejected(lib.vda_gemm_f32(fake, 64, fake, fake, 256, 4096, 256, 64,
+                               _lib.Epilogue(rowbias=0x2000, rdiv=0, rmod=1), None), b"rowbias needs rdiv, rmod > 0")
+    # an unused ldres / ldres2 (no res / res2 pointer) is not looked at
+    e = E(ldres=3, ldres2=5, act=7)
+    _rejected(lib.vda_gemm_f32(fake, 64, fake, fake, 256, 4096, 256, 64, e, None), b"unknown activation")
+
+
+def test_conv2d_f32_rejects_what_its_kernel_ignores():
+    """vda_conv2d_f32: a rowbias needs rdiv, rmod > 0 (the epilogue divides by them on the device), and
+    drop_period, GEGLU, the pixel-shuffle store, misaligned residual rows and the fp16-only fields are
+    refused before any launch."""
+    lib = _lib.lib()
+    fake = ctypes.c_void_p(0x1000)
+    conv = lambda e: lib.vda_conv2d_f32(fake, fake, fake, 2, 9, 11, 32, 64, 3, 1, 1, 0, e, None)  # noqa: E731
+    _rejected(conv(_lib.Epilogue(rowbias=0x2000, rdiv=0, rmod=1)), b"rowbias needs rdiv, rmod > 0")
+    _rejected(conv(_lib.Epilogue(rowbias=0x2000, rdiv=1, rmod=0)), b"rowbias needs rdiv, rmod > 0")
+    _rejected(conv(_lib.Epilogue(rowbias=0x2000, rdiv=-3, rmod=2)), b"rowbias needs rdiv, rmod > 0")
+    _rejected(conv(_lib.Epilogue(rdiv=1, rmod=1, drop_period=300)), b"drop_period")
+    _rejected(conv(_lib.Epilogue(rdiv=1, rmod=1, res=0x2000, ldres=66)), b"ldres a multiple of 4")
+    _rejected(conv(_lib.Epilogue(rdiv=1, rmod=1, res2=0x2000, ldres2=66)), b"ldres2 a multiple of 4")
+    _rejected(conv(_lib.Epilogue(rdiv=1, rmod=1, act=_lib.ACT_GEGLU)), b"no GEGLU / pixel shuffle")
+    _rejected(conv(_lib.Epilogue(rdiv=1, rmod=1, store=_lib.STORE_PIXEL_SHUFFLE)), b"no GEGLU / pixel shuffle")
+    _rejected(conv(_lib.Epilogue(rdiv=1, rmod=1, stats_out=0x2000)), b"no LayerNorm fold / row statistics")
+    _rejected(conv(_lib.Epilogue(rdiv=1, rmod=1, act=7)), b"unknown activation")
+
+
 def test_res2_upsample_validation():
     """An upsampled res2 (vda_epilogue.res2_h/res2_w) is a conv-epilogue option of the halo-tiled
     256-channel route only: the GEMM, the fp32 conv and other conv routes reject it before any launch,

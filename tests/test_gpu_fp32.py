@@ -2,7 +2,8 @@
 
 Parity tier (i) of SURVEY.md §8(d): fp32 mode vs the reference's fp32 goldens, bar rel-L1 <= 1e-5
 (summation-order rounding only).  Per-op tests compare each *_f32 entry point with torch fp32 on the
-CPU at 2e-6 rel-L1 (exact-f32 products, fp32 accumulation in a different order).
+CPU at 2e-6 rel-L1 (exact-f32 products, fp32 accumulation in a different order).  The tile edges, strides,
+grid-stride loops and NaN-neighbour cases of each kernel are in test_gpu_fp32_ops.py.
 """
 import os
 

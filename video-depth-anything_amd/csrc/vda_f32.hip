@@ -516,7 +516,17 @@ extern "C" int vda_gemm_f32(const float* x, int64_t ldx, const float* w, float* 
   VDA_CHECK_ARG(x && w && y && epi, "null pointer");
   VDA_CHECK_ARG(M > 0 && N > 0 && K > 0, "empty GEMM");
   VDA_CHECK_ARG(K % 4 == 0 && ldx % 4 == 0 && N % 4 == 0, "fp32 GEMM needs K, ldx, N multiples of 4");
-  VDA_CHECK_ARG(epi->act != VDA_ACT_GEGLU || N % 32 == 0, "GEGLU needs N % 32 == 0");
+  VDA_CHECK_ARG(ldx >= K, "fp32 GEMM needs ldx >= K");
+  // every row access of the epilogue is a float4: y, res and res2 rows must keep that alignment
+  VDA_CHECK_ARG(ldy % 4 == 0, "fp32 GEMM needs ldy a multiple of 4");
+  VDA_CHECK_ARG(!epi->res || epi->ldres % 4 == 0, "fp32 GEMM needs ldres a multiple of 4");
+  VDA_CHECK_ARG(!epi->res2 || epi->ldres2 % 4 == 0, "fp32 GEMM needs ldres2 a multiple of 4");
+  // the kernel stores all M rows: the cls-row drop exists on vda_gemm's phased route only
+  VDA_CHECK_ARG(epi->drop_period == 0, "fp32 GEMM: no drop_period (vda_gemm only)");
+  // the GEGLU branch of the kernel applies bias, gamma and res, and stores rows
+  VDA_CHECK_ARG(epi->act != VDA_ACT_GEGLU || (N % 32 == 0 && !epi->rowbias && !epi->res2 &&
+                                              epi->store == VDA_STORE_ROWS),
+                "GEGLU needs N % 32 == 0, no rowbias/res2, row store");
   VDA_CHECK_ARG(epi->store != VDA_STORE_PIXEL_SHUFFLE || (epi->ps_k > 0 && epi->ps_cout % 4 == 0 &&
                                                          epi->ps_hin > 0 && epi->ps_win > 0),
                 "bad pixel-shuffle geometry");
@@ -537,6 +547,11 @@ extern "C" int vda_conv2d_f32(const float* x, const float* w, float* y, int32_t 
   VDA_CHECK_ARG(Cin % 4 == 0 && Cout % 4 == 0, "fp32 conv needs Cin, Cout multiples of 4");
   VDA_CHECK_ARG(epi->act != VDA_ACT_GEGLU && epi->store == VDA_STORE_ROWS, "conv epilogue: no GEGLU / pixel shuffle");
   VDA_CHECK_ARG(epi->res2_h == 0 && epi->res2_w == 0, "fp32 conv: no upsampled res2 (materialise it)");
+  VDA_CHECK_ARG(!epi->rowbias || (epi->rdiv > 0 && epi->rmod > 0), "rowbias needs rdiv, rmod > 0");
+  VDA_CHECK_ARG(epi->drop_period == 0, "fp32 conv: no drop_period (vda_gemm only)");
+  VDA_CHECK_ARG(!epi->res || epi->ldres % 4 == 0, "fp32 conv needs ldres a multiple of 4");
+  VDA_CHECK_ARG(!epi->res2 || epi->ldres2 % 4 == 0, "fp32 conv needs ldres2 a multiple of 4");
+  VDA_CHECK_ARG(!epi->ln_stats && !epi->stats_out, "fp32 conv: no LayerNorm fold / row statistics");
   F32Params p{};
   p.x = x; p.w = w; p.y = y; p.ldy = Cout;
   p.H = H; p.W = W; p.Cin = Cin; p.ks = ks; p.stride = stride; p.pad = pad; p.pre_relu = pre_relu;
