@@ -40,3 +40,27 @@ def recipe_state_dict(enc):
 
 def rel_l1(a, b):
     return vda_oracle.rel_l1(a, b)
+
+
+def assert_elementwise(y, ref64, bound64, what):
+    """Assert |y - ref| <= bound at EVERY element (y any dtype / device; ref64, bound64 float64 of y's
+    shape, a bound from tests/fp16_bounds.py).  A non-finite y counts as a violation.  The failure message
+    gives the number of violations, the worst ratio |y - ref| / bound and the worst element's index
+    unravelled over y's shape ((frame, row, column, channel) for an NHWC map, (row, column) for a
+    matrix), so a tile edge can be read off it.  Returns the worst ratio."""
+    y64 = y.detach().to("cpu", torch.float64)
+    ref64, bound64 = ref64.to(torch.float64), bound64.to(torch.float64)
+    assert y64.shape == ref64.shape == bound64.shape, f"{what}: shapes {tuple(y64.shape)} {tuple(ref64.shape)} {tuple(bound64.shape)}"
+    assert bool((bound64 > 0).all()) and bool(torch.isfinite(ref64).all()), f"{what}: bad reference / bound"
+    ratio = (y64 - ref64).abs() / bound64
+    ratio = torch.where(torch.isfinite(y64), ratio, torch.full_like(ratio, float("inf")))
+    worst = float(ratio.max())
+    if worst > 1.0:
+        bad = ratio > 1.0
+        idx = tuple(int(i) for i in np.unravel_index(int(ratio.argmax()), tuple(ratio.shape)))
+        first = tuple(int(i) for i in bad.nonzero()[0])
+        raise AssertionError(
+            f"{what}: {int(bad.sum())} of {ratio.numel()} elements outside the bound; worst |y - ref| / bound = "
+            f"{worst:.3g} at index {idx} of shape {tuple(ratio.shape)} (y {float(y64[idx]):.6g}, ref {float(ref64[idx]):.6g}, "
+            f"bound {float(bound64[idx]):.3g}); first violation at {first}")
+    return worst
