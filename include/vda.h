@@ -354,6 +354,53 @@ int vda_depth_eval_metrics(const float* pred, const float* gt, const uint8_t* va
                            double* frame_sums, double* total, void* ws, int64_t ws_bytes, void* stream);
 
 /*
+ * Depth visualisation on the device (the reference's save_video, utils/dc_utils.py:72-89): the clip-wide
+ * min / max, then fp32 depth straight to the bytes of the output file through a 256-row table.  No atomics,
+ * no allocation, no synchronisation; results stay on the device.
+ *
+ * vda_depth_range: range [2] float (DEVICE) = (min, max) of the n >= 1 floats at depth (dc_utils.py:76).  A
+ *   two-stage reduction (block partials in ws, then one block) with 16-byte loads on the aligned body; depth
+ *   needs 4-byte alignment only.  NaNs are skipped (fminf / fmaxf); an all-NaN input gives (+inf, -inf).
+ *   n is 64-bit.  ws: vda_depth_range_workspace(n) bytes of device memory owned by the caller, 4-byte
+ *   aligned; it needs no initialisation and holds nothing between calls.
+ *
+ * vda_depth_colorize: per pixel of depth [F, H, W] in fp32, every operation correctly rounded (IEEE
+ *   division, no reciprocal, no contraction):
+ *     x = (d - range[0]) / (range[1] - range[0]) * 255.0f;   i = (uint8_t)x by truncation
+ *   which is dc_utils.py:79 as numpy float32 computes it, then out = lut[i] in `layout`.  range [2] float
+ *   (DEVICE) may have been computed over another, larger tensor than depth (the range of the whole video,
+ *   the colouring per chunk).  lut [256, 3] uint8 (DEVICE, any alignment) is staged once per block in LDS;
+ *   the kernel does not know colour spaces: pass RGB rows for RGB output, already converted YUV rows for
+ *   y4m payloads.
+ *   Deviation: x that is NaN (a constant clip gives 0 / 0) or below 0 gives index 0, x above 255 gives 255;
+ *   numpy's cast is undefined there (on x86 it gives 0 for the constant clip, as here).
+ *   Layouts (out holds vda_depth_colorize_bytes(F, H, W, layout) bytes, nothing is written outside them):
+ *     VDA_VIS_INDEX      [F, H, W]      the index itself; lut may be NULL
+ *     VDA_VIS_HWC        [F, H, W, 3]   lut[i] interleaved (what Pillow and imageio take)
+ *     VDA_VIS_PLANAR444  [F, 3, H, W]   plane c holds lut[i][c]: the payload of a y4m C444 frame
+ *     VDA_VIS_PLANAR420  [F, H*W + 2*ch*cw], ch = (H+1)/2, cw = (W+1)/2: per frame the full-size plane 0, then
+ *                        planes 1 and 2 subsampled, each sample (a + b + c + d + 2) >> 2 over the 2x2 block of
+ *                        looked-up values, the last row / column repeated at odd sizes (an exact integer
+ *                        reduction): the payload of a y4m C420 frame
+ *   Neither depth (4-byte aligned) nor out (any address) needs 16-byte alignment: every frame and plane has
+ *   its own bytewise head and tail (at most 3 pixels each) around dword stores.  In the 4:2:0 layout a strip
+ *   of 8 x 2 pixels is stored as dwords when its row address is dword-aligned, and with bytes and 16-bit
+ *   words around a dword otherwise (never at W % 8 == 0 with a 4-byte-aligned out).  1 <= F <= 65535 (the
+ *   launch grid), H, W >= 1.
+ */
+enum {
+  VDA_VIS_INDEX = 0,
+  VDA_VIS_HWC = 1,
+  VDA_VIS_PLANAR444 = 2,
+  VDA_VIS_PLANAR420 = 3
+};
+int64_t vda_depth_range_workspace(int64_t n);
+int vda_depth_range(const float* depth, int64_t n, float* range, void* ws, int64_t ws_bytes, void* stream);
+int64_t vda_depth_colorize_bytes(int32_t F, int32_t H, int32_t W, int32_t layout);
+int vda_depth_colorize(const float* depth, int32_t F, int32_t H, int32_t W, const float* range,
+                       const uint8_t* lut, int32_t layout, uint8_t* out, void* stream);
+
+/*
  * fp32 mode (infer_video_depth(fp32=True) / autocast off, video_depth.py:366-368): the same ops
  * with fp32 activations AND fp32 weights, fp32 accumulation on the exact-f32 MFMA
  * (v_mfma_f32_16x16x4_f32), exact-erf GELU, expf softmax.  Same layouts and epilogue contract as

@@ -10,6 +10,8 @@ source / visualisation videos as .y4m, or .gif/.png/.webp via ``--vis_format``).
 uses the deterministic recipe of vda_amd.weights when no checkpoint is available (this image has none).
 ``--fp32`` selects the fp32 kernels (the reference's autocast-off path); the default is fp16 compute.
 ``--stitch device`` aligns and stitches on the device (vda_scale_shift / vda_depth_align); the default is the host.
+``--vis device`` (with ``--stitch device``) colours the ``--save_vis`` video on the device (vda_depth_range /
+vda_depth_colorize) and writes the same file as the host path; ``--vis_chroma 420`` writes a 4:2:0 .y4m.
 """
 import argparse
 import os
@@ -61,6 +63,11 @@ def add_arguments(p):
     p.add_argument("--stitch", type=str, default="host", choices=["host", "device"],
                    help="where windows (or, with --process_single_image --align_each_new_frame, new frames) are "
                         "aligned and stitched: on the host as the reference does, or on the device")
+    p.add_argument("--vis", type=str, default="host", choices=["host", "device"],
+                   help="where --save_vis colours the depth: in numpy on the host as the reference does, or on the "
+                        "device (needs --stitch device; the same file, without the host passes)")
+    p.add_argument("--vis_chroma", type=str, default="444", choices=["444", "420"],
+                   help="chroma format of a .y4m visualisation: 4:4:4 (3 B per pixel) or 4:2:0 (1.5 B per pixel)")
     return p
 
 
@@ -71,7 +78,10 @@ def check_args(a):
 
 def parse(argv=None):
     p = add_arguments(argparse.ArgumentParser(description="Video Depth Anything (MI355X)"))
-    return check_args(p.parse_args(argv))
+    a = p.parse_args(argv)
+    if a.vis == "device" and a.stitch != "device":
+        p.error("--vis device needs --stitch device (it colours the depth where the device stitcher leaves it)")
+    return check_args(a)
 
 
 def load_model(args):
@@ -104,7 +114,8 @@ def main(argv=None):
     else:
         depths, fps = model.infer_video_depth(frames, target_fps, input_size=args.input_size, device=dev, fp32=args.fp32,
                                               skip_tmp_block=args.skip_tmp_block and not args.original,
-                                              windows_per_batch=max(1, args.windows_per_batch), stitch=args.stitch)
+                                              windows_per_batch=max(1, args.windows_per_batch), stitch=args.stitch,
+                                              **({"return_device": True} if args.vis == "device" else {}))
     dur = time.time() - t0
     os.makedirs(args.output_dir, exist_ok=True)
     stem = os.path.splitext(os.path.basename(args.input_video))[0]
@@ -122,8 +133,14 @@ def main(argv=None):
     if args.save_orig:
         VIO.save_video(frames, os.path.join(args.output_dir, name + "_src" + ext), fps=fps)
     if args.save_vis:
-        VIO.save_video(depths, os.path.join(args.output_dir, name + "_vis" + ext), fps=fps, is_depths=True,
-                       grayscale=args.grayscale, spectral=not args.grayscale)
+        vis_in = depths
+        if args.vis == "device" and not torch.is_tensor(depths):  # the streaming driver returns numpy
+            vis_in = torch.from_numpy(np.ascontiguousarray(depths, dtype=np.float32)).to(dev)
+        VIO.save_video(vis_in, os.path.join(args.output_dir, name + "_vis" + ext), fps=fps, is_depths=True,
+                       grayscale=args.grayscale, spectral=not args.grayscale, chroma=args.vis_chroma)
+        del vis_in
+    if torch.is_tensor(depths):  # --vis device: the float depth leaves the device after the visualisation is written
+        depths = depths.cpu().numpy()
     if args.save_npz:
         VIO.save_npz(os.path.join(args.output_dir, name + "_depths.npz"), depths)
     if args.save_tiff:

@@ -28,6 +28,7 @@ EXPORTED = (
     "vda_depth_head", "vda_depth_head_workspace", "vda_preprocess_frames", "vda_depth_resize",
     "vda_scale_shift", "vda_scale_shift_workspace", "vda_depth_align",
     "vda_depth_eval_workspace", "vda_depth_eval_fit", "vda_depth_eval_metrics",
+    "vda_depth_range_workspace", "vda_depth_range", "vda_depth_colorize_bytes", "vda_depth_colorize",
     "vda_gemm_f32", "vda_conv2d_f32", "vda_layernorm_f32", "vda_groupnorm_f32", "vda_spatial_attention_f32",
     "vda_temporal_attention_f32", "vda_upsample_bilinear_f32", "vda_patch_im2col_f32", "vda_depth_head_f32",
 )
@@ -38,6 +39,7 @@ TUNE_LIB_PATH = os.path.join(os.path.dirname(_HERE), "build", "tune", "libvda.so
 
 ACT_NONE, ACT_GELU, ACT_GEGLU, ACT_RELU = 0, 1, 2, 3
 STORE_ROWS, STORE_PIXEL_SHUFFLE = 0, 1
+VIS_INDEX, VIS_HWC, VIS_PLANAR444, VIS_PLANAR420 = 0, 1, 2, 3  # VDA_VIS_* (vda_depth_colorize layouts)
 
 
 class VDAUnavailable(RuntimeError):
@@ -97,6 +99,10 @@ def _declare(lib):
         "vda_depth_eval_workspace": ([I, L], L),
         "vda_depth_eval_fit": ([P, P, P, I, L, I, P, P, P, L, P], I),
         "vda_depth_eval_metrics": ([P, P, P, I, L, P, I, F, P, P, P, P, L, P], I),
+        "vda_depth_range_workspace": ([L], L),
+        "vda_depth_range": ([P, L, P, P, L, P], I),
+        "vda_depth_colorize_bytes": ([I, I, I, I], L),
+        "vda_depth_colorize": ([P, I, I, I, P, P, I, P, P], I),
         "vda_gemm_f32": ([P, L, P, P, L, I, I, I, EP, P], I),
         "vda_conv2d_f32": ([P, P, P, I, I, I, I, I, I, I, I, I, EP, P], I),
         "vda_layernorm_f32": ([P, L, P, P, P, I, I, F, I, P], I),

@@ -622,9 +622,61 @@ std::tuple<Tensor, Tensor, optional<Tensor>> depth_eval_metrics(const Tensor& pr
   return {frame_sums, total, aligned};
 }
 
+// ---- depth visualisation -----------------------------------------------------------------------
+Tensor depth_range(const Tensor& depth) {
+  TORCH_CHECK(depth.scalar_type() == at::kFloat && depth.is_contiguous() && depth.numel() >= 1,
+              "vda depth_range: depth must be a contiguous, non-empty float tensor");
+  Tensor range = at::empty({2}, depth.options());
+  if (depth.is_meta()) return range;
+  const at::OptionalDeviceGuard g(depth.device());
+  const int64_t n = depth.numel();
+  const int64_t wsb = vda_depth_range_workspace(n);
+  Tensor ws = at::empty({wsb}, depth.options().dtype(at::kByte));
+  check_rc(vda_depth_range((const float*)depth.data_ptr(), n, (float*)range.data_ptr(), ws.data_ptr(), wsb,
+                           stream_of(depth)),
+           "vda_depth_range");
+  return range;
+}
+
+Tensor depth_colorize(const Tensor& depth, const Tensor& range, OptT lut, int64_t layout) {
+  TORCH_CHECK(depth.scalar_type() == at::kFloat && depth.dim() == 3 && depth.is_contiguous() && depth.numel() >= 1,
+              "vda depth_colorize: depth must be a contiguous, non-empty float [F, H, W] tensor");
+  const int64_t F = depth.size(0), H = depth.size(1), W = depth.size(2);
+  TORCH_CHECK(F <= 65535, "vda depth_colorize: F <= 65535 frames per call, got ", F);
+  TORCH_CHECK(H <= INT32_MAX && W <= INT32_MAX, "vda depth_colorize: H and W must fit 32 bits");
+  need_contig(range, at::kFloat, "range", depth);
+  TORCH_CHECK(range.numel() == 2, "vda depth_colorize: range must hold (min, max)");
+  TORCH_CHECK(layout >= VDA_VIS_INDEX && layout <= VDA_VIS_PLANAR420, "vda depth_colorize: unknown layout ", layout);
+  TORCH_CHECK(lut.has_value() || layout == VDA_VIS_INDEX, "vda depth_colorize: this layout needs a lut");
+  if (lut) {
+    need_contig(*lut, at::kByte, "lut", depth);
+    TORCH_CHECK(lut->dim() == 2 && lut->size(0) == 256 && lut->size(1) == 3, "vda depth_colorize: lut must be [256, 3]");
+  }
+  const int64_t ch = (H + 1) / 2, cw = (W + 1) / 2;
+  Tensor out;
+  const auto opt = depth.options().dtype(at::kByte);
+  switch (layout) {
+    case VDA_VIS_INDEX: out = at::empty({F, H, W}, opt); break;
+    case VDA_VIS_HWC: out = at::empty({F, H, W, 3}, opt); break;
+    case VDA_VIS_PLANAR444: out = at::empty({F, 3, H, W}, opt); break;
+    default: out = at::empty({F, H * W + 2 * ch * cw}, opt); break;
+  }
+  if (depth.is_meta()) return out;
+  const at::OptionalDeviceGuard g(depth.device());
+  TORCH_CHECK(out.numel() == vda_depth_colorize_bytes((int32_t)F, (int32_t)H, (int32_t)W, (int32_t)layout),
+              "vda depth_colorize: output size disagrees with vda_depth_colorize_bytes");
+  check_rc(vda_depth_colorize((const float*)depth.data_ptr(), (int32_t)F, (int32_t)H, (int32_t)W,
+                              (const float*)range.data_ptr(), (const uint8_t*)ptr(lut), (int32_t)layout,
+                              (uint8_t*)out.data_ptr(), stream_of(depth)),
+           "vda_depth_colorize");
+  return out;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(vda, m) {
+  m.def("depth_range(Tensor depth) -> Tensor");
+  m.def("depth_colorize(Tensor depth, Tensor range, Tensor? lut, int layout) -> Tensor");
   m.def("gemm(Tensor x, Tensor w, Tensor? bias=None, Tensor? rowbias=None, int rdiv=1, int rmod=1, "
         "Tensor? gamma=None, Tensor? res=None, Tensor? res2=None, int act=0, Tensor? ln_stats=None, "
         "Tensor? ln_colsum=None, int ln_parts=0, float ln_eps=1e-6, Tensor(b!)? stats_out=None, "
@@ -677,6 +729,8 @@ TORCH_LIBRARY(vda, m) {
     m.impl("depth_align", &depth_align);                      \
     m.impl("depth_eval_fit", &depth_eval_fit);                \
     m.impl("depth_eval_metrics", &depth_eval_metrics);        \
+    m.impl("depth_range", &depth_range);                      \
+    m.impl("depth_colorize", &depth_colorize);                \
   }
 
 VDA_IMPL(CUDA)

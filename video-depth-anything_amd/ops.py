@@ -283,3 +283,43 @@ def depth_eval_metrics(pred: Tensor, gt: Tensor, valid: Optional[Tensor], ss: Te
     if not float(max_depth) > 0.:
         raise ValueError(f"max_depth must be greater than 0, got {max_depth}")
     return _vda().depth_eval_metrics(pred, gt, valid, ss, float(max_depth), bool(want_aligned))
+
+
+VIS_LAYOUTS = {"index": _lib.VIS_INDEX, "hwc": _lib.VIS_HWC, "planar444": _lib.VIS_PLANAR444,
+               "planar420": _lib.VIS_PLANAR420}
+
+
+def depth_range(depth: Tensor) -> Tensor:
+    """(min, max) of a contiguous fp32 GPU tensor -> [2] fp32 on the device, NaNs skipped, no host sync
+    (vda.h vda_depth_range)."""
+    if not isinstance(depth, torch.Tensor) or not depth.is_cuda or depth.dtype != torch.float32:
+        raise ValueError("depth must be a float32 GPU tensor (no CPU path in the product)")
+    if depth.numel() < 1 or not depth.is_contiguous():
+        raise ValueError(f"depth must be contiguous and non-empty, got {tuple(depth.shape)}")
+    return _vda().depth_range(depth)
+
+
+def depth_colorize(depth: Tensor, range: Tensor, *, lut: Optional[Tensor] = None, layout="hwc") -> Tensor:
+    """depth [F, H, W] fp32 (GPU) -> uint8: the index ``uint8((d - range[0]) / (range[1] - range[0]) * 255)``
+    of every pixel in fp32, then ``lut[index]`` (``lut`` [256, 3] uint8 on the device) in ``layout``:
+    ``"index"`` [F, H, W] (no lut), ``"hwc"`` [F, H, W, 3], ``"planar444"`` [F, 3, H, W] or ``"planar420"``
+    [F, H*W + 2*ch*cw] (a name or the VDA_VIS_* code).  ``range`` is a device [2] tensor, e.g. ``depth_range``
+    of the whole video (vda.h vda_depth_colorize)."""
+    if not isinstance(depth, torch.Tensor) or not depth.is_cuda or depth.dtype != torch.float32:
+        raise ValueError("depth must be a float32 GPU tensor (no CPU path in the product)")
+    if depth.dim() != 3 or depth.numel() < 1 or not depth.is_contiguous() or depth.shape[0] > 65535:
+        raise ValueError(f"depth must be contiguous, non-empty [F, H, W] with F <= 65535, got {tuple(depth.shape)}")
+    if not isinstance(range, torch.Tensor) or range.dtype != torch.float32 or range.device != depth.device \
+            or range.numel() != 2 or not range.is_contiguous():
+        raise ValueError("range must be a contiguous float32 [2] tensor (min, max) on depth's device")
+    code = VIS_LAYOUTS.get(layout, layout) if isinstance(layout, str) else int(layout)
+    if code not in VIS_LAYOUTS.values():
+        raise ValueError(f"layout must be one of {sorted(VIS_LAYOUTS)}, got {layout!r}")
+    if lut is None:
+        if code != _lib.VIS_INDEX:
+            raise ValueError("every layout but 'index' needs a lut")
+    else:
+        if not isinstance(lut, torch.Tensor) or lut.dtype != torch.uint8 or lut.device != depth.device \
+                or tuple(lut.shape) != (256, 3) or not lut.is_contiguous():
+            raise ValueError("lut must be a contiguous uint8 [256, 3] tensor on depth's device")
+    return _vda().depth_colorize(depth, range, lut, code)

@@ -14,7 +14,8 @@ and encoders that need only numpy / Pillow:
 * ``save_video(frames, path, fps, is_depths, grayscale, spectral)`` (dc_utils.py:72-89): depth is
   min/max-normalised to uint8 over the whole clip and mapped through matplotlib's inferno (or
   Spectral) table; written as ``.y4m`` (4:4:4), or animated GIF / PNG / WebP via Pillow; ``.mp4``
-  needs imageio + ffmpeg and raises a clear error without them.
+  needs imageio + ffmpeg and raises a clear error without them.  ``chroma="420"`` writes a 4:2:0 ``.y4m``;
+  depth given as a CUDA tensor is coloured on the device (vda_amd.visualize) and gives the same files.
 * ``save_npz`` (``depths`` key, run.py:162-164) and ``save_tiff`` (float32 multi-page, :165-166).
 
 YUV <-> RGB uses BT.601 limited range (ffmpeg's default for SD/unknown-matrix y4m); decoded frames
@@ -119,17 +120,35 @@ def read_y4m(path: str) -> Tuple[np.ndarray, float]:
     return np.stack(frames), fps
 
 
-def write_y4m(path: str, frames: np.ndarray, fps: float):
-    """RGB (or grey) uint8 frames -> YUV4MPEG2 4:4:4 (C444), BT.601 limited range."""
+def _subsample_420(p: np.ndarray) -> np.ndarray:
+    """uint8 [h, w] -> [(h+1)//2, (w+1)//2]: (a + b + c + d + 2) >> 2 over 2x2 blocks (an exact integer
+    average, sited between the four samples as C420jpeg is), the last row / column repeated at odd sizes."""
+    p = np.pad(p.astype(np.int32), ((0, p.shape[0] % 2), (0, p.shape[1] % 2)), mode="edge")
+    return ((p[0::2, 0::2] + p[0::2, 1::2] + p[1::2, 0::2] + p[1::2, 1::2] + 2) >> 2).astype(np.uint8)
+
+
+def _y4m_header(w: int, h: int, fps: float, chroma: str) -> bytes:
+    if chroma not in ("444", "420"):
+        raise ValueError(f"chroma must be '444' or '420', got {chroma!r}")
+    num, den = (int(round(fps * 1001)), 1001) if abs(fps * 1001 - round(fps * 1001)) < 1e-6 else (int(round(fps * 1000)), 1000)
+    cs = "C444" if chroma == "444" else "C420jpeg"
+    return f"YUV4MPEG2 W{w} H{h} F{num}:{den} Ip A1:1 {cs}\n".encode("ascii")
+
+
+def write_y4m(path: str, frames: np.ndarray, fps: float, chroma: str = "444"):
+    """RGB (or grey) uint8 frames -> YUV4MPEG2, BT.601 limited range: 4:4:4 (C444), or with ``chroma="420"``
+    4:2:0 (C420jpeg), the chroma planes averaged over 2x2 blocks (``_subsample_420``)."""
     frames = np.asarray(frames)
     if frames.ndim == 3:
         frames = np.repeat(frames[..., None], 3, -1)
     n, h, w, _ = frames.shape
-    num, den = (int(round(fps * 1001)), 1001) if abs(fps * 1001 - round(fps * 1001)) < 1e-6 else (int(round(fps * 1000)), 1000)
+    head = _y4m_header(w, h, fps, chroma)
     with open(path, "wb") as f:
-        f.write(f"YUV4MPEG2 W{w} H{h} F{num}:{den} Ip A1:1 C444\n".encode("ascii"))
+        f.write(head)
         for i in range(n):
             y, u, v = _rgb_to_yuv(frames[i])
+            if chroma == "420":
+                u, v = _subsample_420(u), _subsample_420(v)
             f.write(b"FRAME\n")
             f.write(y.tobytes())
             f.write(u.tobytes())
@@ -223,12 +242,57 @@ def colorize_depths(depths: np.ndarray, grayscale: bool = False, spectral: bool 
     return (table[norm] * 255).astype(np.uint8)
 
 
+def _is_cuda_tensor(x) -> bool:
+    return type(x).__module__.split(".")[0] == "torch" and bool(getattr(x, "is_cuda", False))
+
+
+def _save_depth_video_device(depth, output_video_path: str, fps: float, grayscale: bool, spectral: bool, chroma: str):
+    """``save_video`` for depth that lies on the device (vda_amd.visualize): the frames arrive from the
+    device as y4m payloads (planar YUV, 4:4:4 or 4:2:0) and are written as they arrive, or as RGB / grey
+    frames for Pillow and imageio.  The same bytes as the host path writes for the same depth."""
+    from .visualize import colorize_depths_device
+    ext = os.path.splitext(output_video_path)[1].lower()
+    if ext == ".y4m":
+        _, h, w = depth.shape
+        head = _y4m_header(w, h, fps, chroma)
+        with open(output_video_path, "wb") as f:
+            f.write(head)
+            for block in colorize_depths_device(depth, grayscale, spectral, layout="planar" + chroma):
+                for payload in block:
+                    f.write(b"FRAME\n")
+                    f.write(payload.tobytes())
+        return
+    chunks = colorize_depths_device(depth, grayscale, spectral, layout="index" if grayscale else "hwc")
+    if ext in (".gif", ".png", ".webp", ".apng"):
+        from PIL import Image
+        ims = [Image.fromarray(f.copy()) for block in chunks for f in block]
+        ims[0].save(output_video_path, save_all=True, append_images=ims[1:], duration=int(round(1000 / fps)), loop=0)
+        return
+    try:
+        import imageio
+    except ImportError as e:
+        raise RuntimeError(f"{output_video_path}: mp4 output needs imageio + ffmpeg (not installed); use .y4m, .gif, "
+                           ".png or .webp") from e
+    writer = imageio.get_writer(output_video_path, fps=fps, macro_block_size=1, codec="libx264",
+                                ffmpeg_params=["-crf", "18"])
+    for block in chunks:
+        for f in block:
+            writer.append_data(f)
+    writer.close()
+
+
 def save_video(frames: np.ndarray, output_video_path: str, fps: float = 10, is_depths: bool = False,
-               grayscale: bool = False, spectral: bool = False):
+               grayscale: bool = False, spectral: bool = False, chroma: str = "444"):
+    """``frames``: uint8 frames, or with ``is_depths`` float depth [N, h, w]; depth given as a CUDA tensor is
+    coloured on the device (``_save_depth_video_device``), numpy input on the host.  ``chroma``: the chroma
+    format of a ``.y4m`` output, "444" or "420"."""
+    if is_depths and _is_cuda_tensor(frames):
+        _save_depth_video_device(frames, output_video_path, fps, grayscale, spectral, chroma)
+        return
     vis = colorize_depths(frames, grayscale, spectral) if is_depths else np.asarray(frames)
     ext = os.path.splitext(output_video_path)[1].lower()
     if ext == ".y4m":
-        write_y4m(output_video_path, vis, fps)
+        write_y4m(output_video_path, vis, fps, chroma)
         return
     if ext in (".gif", ".png", ".webp", ".apng"):
         from PIL import Image
