@@ -401,6 +401,45 @@ int vda_depth_colorize(const float* depth, int32_t F, int32_t H, int32_t W, cons
                        const uint8_t* lut, int32_t layout, uint8_t* out, void* stream);
 
 /*
+ * Planar YUV frames, as a YUV4MPEG2 (.y4m) file holds them, to RGB and to the network input, so that a video
+ * is uploaded as the bytes of its file (1.5 B per pixel at 4:2:0) and never decoded on the host.  No atomics, no
+ * allocation, no synchronisation, capturable in a graph.
+ *
+ * Source: src holds N frames, frame n at src + n * frame_stride bytes (frame_stride >= the payload size below,
+ * so frames may be padded).  Within a frame the Y plane (h * w bytes) comes first, then U, then V, ch * cw
+ * bytes each:
+ *   VDA_YUV_420   cw = (w+1)/2, ch = (h+1)/2      VDA_YUV_422   cw = (w+1)/2, ch = h
+ *   VDA_YUV_444   cw = w, ch = h                  VDA_YUV_MONO  no chroma planes, u = v = 128
+ * src (DEVICE) may have any byte alignment; wider loads are used only where an address allows them.
+ *
+ * vda_yuv_to_rgb: out uint8 [N, h, w, 3] (any alignment).  Chroma is taken nearest, u[y >> sy][x >> sx], then
+ *   BT.601 limited range -> RGB in fp32, every operation rounded once, no contraction:
+ *     yf = (y - 16) * float(255.0 / 219.0);  uf = (u - 128) * float(255.0 / 224.0);  vf likewise
+ *     r = yf + 1.402f * vf;  g = (yf - 0.344136f * uf) - 0.714136f * vf;  b = yf + 1.772f * uf
+ *   then rintf (ties to even), clamp to 0..255, cast: the bits numpy float32 gives.  h, N <= 65535 (the grid).
+ *
+ * vda_preprocess_yuv: out float [N, 3, H, W] = vda_preprocess_frames applied to the RGB frames above, bit for
+ *   bit (both kernels instantiate one device function).  Two routes, chosen from (h, w, H, W) alone: a
+ *   workgroup converts the source footprint of its tile of output pixels once into LDS and interpolates from
+ *   there; when a strong downscale makes that footprint exceed the compiled capacity, vda_yuv_to_rgb into ws
+ *   followed by the RGB kernel.  ws: vda_preprocess_yuv_workspace(N, h, w, H, W) bytes of device memory owned
+ *   by the caller, 0 when the tile route serves the shape (ws may be NULL then); it needs no initialisation.
+ *   H, N <= 65535; on the workspace route also h <= 65535.
+ */
+enum {
+  VDA_YUV_420 = 0,
+  VDA_YUV_422 = 1,
+  VDA_YUV_444 = 2,
+  VDA_YUV_MONO = 3
+};
+int vda_yuv_to_rgb(const uint8_t* src, int32_t N, int32_t h, int32_t w, int64_t frame_stride, int32_t chroma,
+                   uint8_t* out, void* stream);
+int64_t vda_preprocess_yuv_workspace(int32_t N, int32_t h, int32_t w, int32_t H, int32_t W);
+int vda_preprocess_yuv(const uint8_t* src, int32_t N, int32_t h, int32_t w, int64_t frame_stride, int32_t chroma,
+                       float* out, int32_t H, int32_t W, const float* mean, const float* stdv, void* ws,
+                       int64_t ws_bytes, void* stream);
+
+/*
  * fp32 mode (infer_video_depth(fp32=True) / autocast off, video_depth.py:366-368): the same ops
  * with fp32 activations AND fp32 weights, fp32 accumulation on the exact-f32 MFMA
  * (v_mfma_f32_16x16x4_f32), exact-erf GELU, expf softmax.  Same layouts and epilogue contract as

@@ -12,6 +12,8 @@ uses the deterministic recipe of vda_amd.weights when no checkpoint is available
 ``--stitch device`` aligns and stitches on the device (vda_scale_shift / vda_depth_align); the default is the host.
 ``--vis device`` (with ``--stitch device``) colours the ``--save_vis`` video on the device (vda_depth_range /
 vda_depth_colorize) and writes the same file as the host path; ``--vis_chroma 420`` writes a 4:2:0 .y4m.
+``--decode device`` (a .y4m input) indexes the file instead of decoding it: every window batch uploads the planar
+YUV bytes of its frames and vda_preprocess_yuv decodes them into the network input; the depth is the same.
 """
 import argparse
 import os
@@ -68,6 +70,10 @@ def add_arguments(p):
                         "device (needs --stitch device; the same file, without the host passes)")
     p.add_argument("--vis_chroma", type=str, default="444", choices=["444", "420"],
                    help="chroma format of a .y4m visualisation: 4:4:4 (3 B per pixel) or 4:2:0 (1.5 B per pixel)")
+    p.add_argument("--decode", type=str, default="host", choices=["host", "device"],
+                   help="where a .y4m input is decoded: on the host (numpy, the whole file up front), or on the "
+                        "device, from the file's YUV bytes as each window needs them (the same depth; needs a "
+                        ".y4m input, a CUDA device and no --max_res downscale)")
     return p
 
 
@@ -81,7 +87,27 @@ def parse(argv=None):
     a = p.parse_args(argv)
     if a.vis == "device" and a.stitch != "device":
         p.error("--vis device needs --stitch device (it colours the depth where the device stitcher leaves it)")
+    if a.decode == "device":
+        if os.path.splitext(a.input_video)[1].lower() != ".y4m":
+            p.error("--decode device needs a .y4m input (it uploads the file's planar YUV frames); convert the video "
+                    "(ffmpeg -i in.mp4 -f yuv4mpegpipe out.y4m) or pass --decode host")
+        if torch.device(a.device).type != "cuda":
+            p.error("--decode device needs a CUDA device")
     return check_args(a)
+
+
+def open_input(args):
+    """The input frames and their rate: decoded on the host (``--decode host``), or with ``--decode device`` the
+    indexed .y4m file (``video_io.Y4MFrames``), which refuses a ``--max_res`` that would downscale it."""
+    from vda_amd import video_io as VIO
+    if args.decode != "device":
+        return VIO.read_video_frames(args.input_video, args.max_len, args.target_fps, args.max_res)
+    frames, fps = VIO.open_y4m(args.input_video, args.max_len, args.target_fps)
+    if args.max_res > 0 and max(frames.h, frames.w) > args.max_res:
+        sys.exit(f"{args.input_video}: --decode device does not downscale ({frames.w}x{frames.h} exceeds --max_res "
+                 f"{args.max_res}; the host path does that step with Pillow's antialiased bicubic): pass --max_res -1 "
+                 "or --decode host")
+    return frames, fps
 
 
 def load_model(args):
@@ -99,14 +125,19 @@ def load_model(args):
 def main(argv=None):
     args = parse(argv)
     from vda_amd import video_io as VIO
+    if args.decode == "device":  # index the file first: a refused input should not cost a model load
+        frames, target_fps = open_input(args)
     model = load_model(args)
     dev = args.device
     if args.save_stats:
         torch.cuda.reset_peak_memory_stats(dev)
-    frames, target_fps = VIO.read_video_frames(args.input_video, args.max_len, args.target_fps, args.max_res)
+    if args.decode != "device":
+        frames, target_fps = open_input(args)
     total = len(frames)
     t0 = time.time()
     if args.process_single_image:  # checked before --original, as in the reference (run.py:93-100)
+        if args.decode == "device":  # the streaming driver takes RGB frames: decoded on the host
+            frames = frames.rgb()
         depths, fps = model.infere_single_image(frames, target_fps, device=dev, fp32=args.fp32, input_size=args.input_size,
                                                 inference_length=args.inference_length, keyframe_list=args.keyframe_list,
                                                 align_each_new_frame=args.align_each_new_frame, warmup=True,

@@ -29,6 +29,7 @@ EXPORTED = (
     "vda_scale_shift", "vda_scale_shift_workspace", "vda_depth_align",
     "vda_depth_eval_workspace", "vda_depth_eval_fit", "vda_depth_eval_metrics",
     "vda_depth_range_workspace", "vda_depth_range", "vda_depth_colorize_bytes", "vda_depth_colorize",
+    "vda_yuv_to_rgb", "vda_preprocess_yuv_workspace", "vda_preprocess_yuv",
     "vda_gemm_f32", "vda_conv2d_f32", "vda_layernorm_f32", "vda_groupnorm_f32", "vda_spatial_attention_f32",
     "vda_temporal_attention_f32", "vda_upsample_bilinear_f32", "vda_patch_im2col_f32", "vda_depth_head_f32",
 )
@@ -40,6 +41,7 @@ TUNE_LIB_PATH = os.path.join(os.path.dirname(_HERE), "build", "tune", "libvda.so
 ACT_NONE, ACT_GELU, ACT_GEGLU, ACT_RELU = 0, 1, 2, 3
 STORE_ROWS, STORE_PIXEL_SHUFFLE = 0, 1
 VIS_INDEX, VIS_HWC, VIS_PLANAR444, VIS_PLANAR420 = 0, 1, 2, 3  # VDA_VIS_* (vda_depth_colorize layouts)
+YUV_420, YUV_422, YUV_444, YUV_MONO = 0, 1, 2, 3  # VDA_YUV_* (vda_yuv_to_rgb / vda_preprocess_yuv chroma codes)
 
 
 class VDAUnavailable(RuntimeError):
@@ -103,6 +105,9 @@ def _declare(lib):
         "vda_depth_range": ([P, L, P, P, L, P], I),
         "vda_depth_colorize_bytes": ([I, I, I, I], L),
         "vda_depth_colorize": ([P, I, I, I, P, P, I, P, P], I),
+        "vda_yuv_to_rgb": ([P, I, I, I, L, I, P, P], I),
+        "vda_preprocess_yuv_workspace": ([I, I, I, I, I], L),
+        "vda_preprocess_yuv": ([P, I, I, I, L, I, P, I, I, POINTER(F), POINTER(F), P, L, P], I),
         "vda_gemm_f32": ([P, L, P, P, L, I, I, I, EP, P], I),
         "vda_conv2d_f32": ([P, P, P, I, I, I, I, I, I, I, I, I, EP, P], I),
         "vda_layernorm_f32": ([P, L, P, P, P, I, I, F, I, P], I),

@@ -12,67 +12,33 @@
 // Both are HBM/latency-bound elementwise gathers: one thread per output pixel, consecutive
 // threads on consecutive output columns so every store is a coalesced row segment; the 4x4 (or
 // 2x2) source window of neighbouring threads overlaps and is served from L1/L2.
-#include "vda_common.h"
+#include "vda_preprocess.h"
 #include "../../include/vda.h"
 
 namespace {
 
-constexpr float kCubicA = -0.75f;
+using vda_pre::NormArgs;
 
-// torch upsample_bicubic2d / cv2 INTER_CUBIC kernel weights for fractional offset t
-__device__ __forceinline__ void cubic_weights(float t, float w[4]) {
-  const float A = kCubicA;
-  const float x0 = t + 1.f;   // |x| in (1, 2)
-  const float x1 = t;         // |x| in [0, 1]
-  const float x2 = 1.f - t;   // |x| in [0, 1]
-  const float x3 = 2.f - t;   // |x| in (1, 2)
-  w[0] = ((A * x0 - 5.f * A) * x0 + 8.f * A) * x0 - 4.f * A;
-  w[1] = ((A + 2.f) * x1 - (A + 3.f)) * x1 * x1 + 1.f;
-  w[2] = ((A + 2.f) * x2 - (A + 3.f)) * x2 * x2 + 1.f;
-  w[3] = ((A * x3 - 5.f * A) * x3 + 8.f * A) * x3 - 4.f * A;
-}
-
-struct NormArgs {
-  float mean[3];
-  float std_[3];
+// Source pixel (y, x) of an interleaved RGB frame.
+struct RgbFetch {
+  const uint8_t* frame;
+  int w;
+  __device__ __forceinline__ vda_pre::Px operator()(int y, int x) const {
+    const uint8_t* p = frame + ((size_t)y * w + x) * 3;
+    return {{vda_pre::unit_scale(p[0]), vda_pre::unit_scale(p[1]), vda_pre::unit_scale(p[2])}};
+  }
 };
 
+// The per-pixel arithmetic is vda_pre::preprocess_pixel, shared with vda_preprocess_yuv (vda_decode.hip).
 __global__ __launch_bounds__(256) void preprocess_kernel(const uint8_t* __restrict__ src, float* __restrict__ dst,
                                                          int h, int w, int H, int W, NormArgs na) {
   const int ox = blockIdx.x * 256 + threadIdx.x;
   const int oy = blockIdx.y;
   const int n = blockIdx.z;
   if (ox >= W) return;
-  // half-pixel source coordinates, not clamped (cubic), floor + fraction (torch
-  // area_pixel_compute_source_index(cubic=true))
-  const float sy = (float)h / (float)H * ((float)oy + 0.5f) - 0.5f;
-  const float sx = (float)w / (float)W * ((float)ox + 0.5f) - 0.5f;
-  const float fy = floorf(sy), fx = floorf(sx);
-  const int iy = (int)fy, ix = (int)fx;
-  float wy[4], wx[4];
-  cubic_weights(sy - fy, wy);
-  cubic_weights(sx - fx, wx);
-  int cols[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) cols[k] = min(max(ix - 1 + k, 0), w - 1) * 3;
-  const uint8_t* frame = src + (size_t)n * h * w * 3;
-  float acc[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const uint8_t* row = frame + (size_t)min(max(iy - 1 + r, 0), h - 1) * w * 3;
-    float rv[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) rv[c] += (float)row[cols[k] + c] / 255.f * wx[k];
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) acc[c] += rv[c] * wy[r];
-  }
+  const RgbFetch fetch{src + (size_t)n * h * w * 3, w};
   const size_t plane = (size_t)H * W;
-  float* out = dst + (size_t)n * 3 * plane + (size_t)oy * W + ox;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) out[c * plane] = (acc[c] - na.mean[c]) / na.std_[c];
+  vda_pre::preprocess_pixel(fetch, h, w, H, W, oy, ox, na, dst + (size_t)n * 3 * plane + (size_t)oy * W + ox, plane);
 }
 
 __global__ __launch_bounds__(256) void depth_resize_kernel(const float* __restrict__ src, float* __restrict__ dst,

@@ -672,9 +672,61 @@ Tensor depth_colorize(const Tensor& depth, const Tensor& range, OptT lut, int64_
   return out;
 }
 
+// ---- planar YUV frames -------------------------------------------------------------------------
+// payload [N, frame_stride] uint8 with unit stride along a frame (any base address): the frames' planar bytes.
+int64_t yuv_frame_stride(const Tensor& payload, int64_t h, int64_t w, int64_t chroma, const char* what) {
+  TORCH_CHECK(payload.scalar_type() == at::kByte && payload.dim() == 2, what, ": payload must be uint8 [N, frame_stride]");
+  TORCH_CHECK(payload.size(1) <= 1 || payload.stride(1) == 1, what, ": payload rows must have unit stride");
+  TORCH_CHECK(h >= 1 && w >= 1 && h <= INT32_MAX && w <= INT32_MAX, what, ": h and w must be positive and fit 32 bits");
+  TORCH_CHECK(chroma >= VDA_YUV_420 && chroma <= VDA_YUV_MONO, what, ": unknown chroma code ", chroma);
+  const int64_t sx = (chroma == VDA_YUV_420 || chroma == VDA_YUV_422) ? 1 : 0, sy = chroma == VDA_YUV_420 ? 1 : 0;
+  const int64_t fsz = h * w + (chroma == VDA_YUV_MONO ? 0 : 2 * ((w + sx) >> sx) * ((h + sy) >> sy));
+  TORCH_CHECK(payload.size(1) >= fsz, what, ": a frame holds ", payload.size(1), " bytes, its payload needs ", fsz);
+  const int64_t stride = payload.size(0) > 1 ? payload.stride(0) : payload.size(1);
+  TORCH_CHECK(stride >= payload.size(1), what, ": payload frames overlap");
+  return stride;
+}
+
+Tensor yuv_to_rgb(const Tensor& payload, int64_t h, int64_t w, int64_t chroma) {
+  const int64_t stride = yuv_frame_stride(payload, h, w, chroma, "vda yuv_to_rgb");
+  const int64_t N = payload.size(0);
+  TORCH_CHECK(N <= 65535 && h <= 65535, "vda yuv_to_rgb: N and h <= 65535 per call");
+  Tensor out = at::empty({N, h, w, 3}, payload.options());
+  if (payload.is_meta() || N == 0) return out;
+  const at::OptionalDeviceGuard g(payload.device());
+  check_rc(vda_yuv_to_rgb((const uint8_t*)payload.data_ptr(), (int32_t)N, (int32_t)h, (int32_t)w, stride,
+                          (int32_t)chroma, (uint8_t*)out.data_ptr(), stream_of(payload)),
+           "vda_yuv_to_rgb");
+  return out;
+}
+
+Tensor preprocess_yuv(const Tensor& payload, int64_t h, int64_t w, int64_t chroma, int64_t H, int64_t W,
+                      at::ArrayRef<double> mean, at::ArrayRef<double> std) {
+  const int64_t stride = yuv_frame_stride(payload, h, w, chroma, "vda preprocess_yuv");
+  TORCH_CHECK(mean.size() == 3 && std.size() == 3, "vda preprocess_yuv: mean / std need 3 values");
+  TORCH_CHECK(H >= 1 && W >= 1 && H <= INT32_MAX && W <= INT32_MAX, "vda preprocess_yuv: H and W must be positive");
+  const int64_t N = payload.size(0);
+  TORCH_CHECK(N <= 65535, "vda preprocess_yuv: N <= 65535 frames per call");
+  Tensor out = at::empty({N, 3, H, W}, payload.options().dtype(at::kFloat));
+  if (payload.is_meta() || N == 0) return out;
+  const at::OptionalDeviceGuard g(payload.device());
+  const float m3[3] = {(float)mean[0], (float)mean[1], (float)mean[2]};
+  const float s3[3] = {(float)std[0], (float)std[1], (float)std[2]};
+  const int64_t wsb = vda_preprocess_yuv_workspace((int32_t)N, (int32_t)h, (int32_t)w, (int32_t)H, (int32_t)W);
+  Tensor ws;
+  if (wsb > 0) ws = at::empty({wsb}, payload.options());
+  check_rc(vda_preprocess_yuv((const uint8_t*)payload.data_ptr(), (int32_t)N, (int32_t)h, (int32_t)w, stride,
+                              (int32_t)chroma, (float*)out.data_ptr(), (int32_t)H, (int32_t)W, m3, s3,
+                              wsb > 0 ? ws.data_ptr() : nullptr, wsb, stream_of(payload)),
+           "vda_preprocess_yuv");
+  return out;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(vda, m) {
+  m.def("yuv_to_rgb(Tensor payload, int h, int w, int chroma) -> Tensor");
+  m.def("preprocess_yuv(Tensor payload, int h, int w, int chroma, int H, int W, float[] mean, float[] std) -> Tensor");
   m.def("depth_range(Tensor depth) -> Tensor");
   m.def("depth_colorize(Tensor depth, Tensor range, Tensor? lut, int layout) -> Tensor");
   m.def("gemm(Tensor x, Tensor w, Tensor? bias=None, Tensor? rowbias=None, int rdiv=1, int rmod=1, "
@@ -731,6 +783,8 @@ TORCH_LIBRARY(vda, m) {
     m.impl("depth_eval_metrics", &depth_eval_metrics);        \
     m.impl("depth_range", &depth_range);                      \
     m.impl("depth_colorize", &depth_colorize);                \
+    m.impl("yuv_to_rgb", &yuv_to_rgb);                        \
+    m.impl("preprocess_yuv", &preprocess_yuv);                \
   }
 
 VDA_IMPL(CUDA)

@@ -323,3 +323,35 @@ def depth_colorize(depth: Tensor, range: Tensor, *, lut: Optional[Tensor] = None
                 or tuple(lut.shape) != (256, 3) or not lut.is_contiguous():
             raise ValueError("lut must be a contiguous uint8 [256, 3] tensor on depth's device")
     return _vda().depth_colorize(depth, range, lut, code)
+
+
+YUV_CHROMA = {"420": _lib.YUV_420, "422": _lib.YUV_422, "444": _lib.YUV_444, "mono": _lib.YUV_MONO}
+
+
+def _yuv_inputs(payload: Tensor, h: int, w: int, chroma):
+    if not isinstance(payload, torch.Tensor) or not payload.is_cuda or payload.dtype != torch.uint8:
+        raise ValueError("payload must be a uint8 GPU tensor (no CPU path in the product)")
+    code = YUV_CHROMA.get(chroma, chroma) if isinstance(chroma, str) else int(chroma)
+    if code not in YUV_CHROMA.values():
+        raise ValueError(f"chroma must be one of {sorted(YUV_CHROMA)}, got {chroma!r}")
+    if payload.dim() != 2 or (payload.shape[1] > 1 and payload.stride(1) != 1) or payload.shape[0] > 65535:
+        raise ValueError(f"payload must be [N, frame_stride] with unit-stride rows and N <= 65535, got "
+                         f"{tuple(payload.shape)}")
+    return int(h), int(w), code
+
+
+def yuv_to_rgb(payload: Tensor, h: int, w: int, chroma) -> Tensor:
+    """Planar YUV frames ``payload`` [N, frame_stride] uint8 (GPU; Y, U, V planes of an h x w frame per row, as a
+    .y4m file holds them, any base alignment) -> RGB uint8 [N, h, w, 3], the bits of ``video_io.read_y4m``.
+    ``chroma``: "420", "422", "444", "mono" or the VDA_YUV_* code (vda.h vda_yuv_to_rgb)."""
+    h, w, code = _yuv_inputs(payload, h, w, chroma)
+    return _vda().yuv_to_rgb(payload, h, w, code)
+
+
+def preprocess_yuv(payload: Tensor, h: int, w: int, chroma, H: int, W: int, mean=(0.485, 0.456, 0.406),
+                   std=(0.229, 0.224, 0.225)) -> Tensor:
+    """Planar YUV frames (as ``yuv_to_rgb`` takes them) -> normalised network input [N, 3, H, W] fp32:
+    ``preprocess_frames(yuv_to_rgb(payload, ...), H, W)`` bit for bit, without the RGB frames in memory unless
+    the downscale is too strong for the tile kernel (vda.h vda_preprocess_yuv)."""
+    h, w, code = _yuv_inputs(payload, h, w, chroma)
+    return _vda().preprocess_yuv(payload, h, w, code, int(H), int(W), [float(v) for v in mean], [float(v) for v in std])

@@ -29,6 +29,8 @@ from typing import Callable, List, Optional, Sequence
 import numpy as np
 import torch
 
+from .video_io import Y4MFrames
+
 INFER_LEN = 32
 OVERLAP = 10
 KEYFRAMES = [0, 12, 24, 25, 26, 27, 28, 29, 30, 31]
@@ -96,6 +98,14 @@ class DeviceIO:
     def preprocess(frames: torch.Tensor, size: tuple) -> torch.Tensor:
         from . import ops
         return ops.preprocess_frames(frames, int(size[0]), int(size[1]), MEAN, STD)
+
+    @staticmethod
+    def preprocess_planar(payload: torch.Tensor, frames, size: tuple) -> torch.Tensor:
+        """``preprocess`` from the planar YUV bytes of the frames (``payload`` [N, frame_stride] uint8 on the
+        device, rows as ``frames``, a ``video_io.Y4MFrames``, hands them out): vda_preprocess_yuv, the bits
+        ``preprocess`` gives for the host-decoded frames."""
+        from . import ops
+        return ops.preprocess_yuv(payload, frames.h, frames.w, frames.chroma, int(size[0]), int(size[1]), MEAN, STD)
 
     @staticmethod
     def resize_depth(depth: torch.Tensor, size: tuple) -> torch.Tensor:
@@ -480,27 +490,54 @@ class _HostSource:
         self.frames, self.dev = frames, device
         self.gpu = device.type == "cuda"
         self.slots: list = []  # [pinned tensor, event or None]
+        self.row = tuple(frames.shape[1:])
+        self.dtype = frames.dtype
+
+    def _gather(self, idx: List[int], out: torch.Tensor):
+        torch.index_select(self.frames, 0, torch.as_tensor(idx, dtype=torch.long), out=out)
 
     def get(self, idx: List[int]) -> torch.Tensor:
-        ix = torch.as_tensor(idx, dtype=torch.long)
         if not self.gpu or self.frames.device.type != "cpu":  # CPU run, or frames already on a device
+            ix = torch.as_tensor(idx, dtype=torch.long)
             return self.frames[ix.to(self.frames.device)].to(self.dev)
-        shape = (len(idx),) + tuple(self.frames.shape[1:])
+        return self._upload(idx)
+
+    def _upload(self, idx: List[int]) -> torch.Tensor:
+        shape = (len(idx),) + self.row
         slot = next((s for s in self.slots if tuple(s[0].shape) == shape and (s[1] is None or s[1].query())), None)
         if slot is None:
             if len(self.slots) >= 2:
                 slot = self.slots.pop(0)
                 slot[1].synchronize()
                 if tuple(slot[0].shape) != shape:
-                    slot[0] = torch.empty(shape, dtype=self.frames.dtype, pin_memory=True)
+                    slot[0] = torch.empty(shape, dtype=self.dtype, pin_memory=True)
             else:
-                slot = [torch.empty(shape, dtype=self.frames.dtype, pin_memory=True), None]
+                slot = [torch.empty(shape, dtype=self.dtype, pin_memory=True), None]
             self.slots.append(slot)
-        torch.index_select(self.frames, 0, ix, out=slot[0])
+        self._gather(idx, slot[0])
         x = slot[0].to(self.dev, non_blocking=True)
         slot[1] = torch.cuda.Event()
         slot[1].record()
         return x
+
+
+class _PlanarSource(_HostSource):
+    """``_HostSource`` for a ``video_io.Y4MFrames`` on a GPU run: a window batch's frames are copied out of the
+    memory-mapped file as planar YUV rows [n, frame_stride] (1.5 bytes per pixel at 4:2:0, never decoded on the
+    host) into the pinned staging buffers and uploaded non-blocking."""
+
+    def __init__(self, frames, device: torch.device):
+        self.frames, self.dev = frames, device
+        self.gpu = True
+        self.slots = []
+        self.row = (int(frames.frame_stride),)
+        self.dtype = torch.uint8
+
+    def _gather(self, idx: List[int], out: torch.Tensor):
+        self.frames.payload(idx, out=out.numpy())
+
+    def get(self, idx: List[int]) -> torch.Tensor:
+        return self._upload(idx)
 
 
 def _gather_round(buf: torch.Tensor, rank: int, world: int, group):
@@ -519,7 +556,10 @@ def infer_video_depth(forward: Callable[[torch.Tensor], torch.Tensor], frames, t
                       device="cuda", windows_per_batch: int = 1, rank: int = 0, world: int = 1, group=None,
                       io=DeviceIO, streams: int = 2, prepare: Optional[Callable[[tuple], None]] = None,
                       stitch: str = "host", return_device: bool = False, align=DeviceAlign):
-    """Depth for every frame of ``frames`` (uint8 [N, h, w, 3] numpy or tensor).
+    """Depth for every frame of ``frames`` (uint8 [N, h, w, 3] numpy or tensor, or a ``video_io.Y4MFrames``:
+    on a GPU with an ``io`` that has ``preprocess_planar`` its frames are uploaded as the planar YUV bytes of the
+    file and decoded by the preprocessing kernel, otherwise they are decoded on the host first; the depth is the
+    same bit for bit).
 
     ``forward(x[B, 32, 3, H, W]) -> depth[B, 32, H, W]`` is the clip forward (the model, or any
     callable); ``prepare((H, W))``, when given, builds whatever state the forward creates lazily
@@ -546,20 +586,26 @@ def infer_video_depth(forward: Callable[[torch.Tensor], torch.Tensor], frames, t
         raise ValueError(f"stitch must be 'host' or 'device', got {stitch!r}")
     if return_device and stitch != "device":
         raise ValueError("return_device=True needs stitch='device' (the host stitcher returns numpy)")
-    if not isinstance(frames, torch.Tensor):
+    dev = torch.device(device)
+    planar = None
+    if isinstance(frames, Y4MFrames):
+        if dev.type == "cuda" and callable(getattr(io, "preprocess_planar", None)):
+            planar = frames          # the window batches upload the file's YUV bytes
+        else:
+            frames = frames.rgb()    # a CPU run, or an io without the planar kernel: decode on the host
+    if planar is None and not isinstance(frames, torch.Tensor):
         frames = torch.from_numpy(np.ascontiguousarray(frames))
     n = frames.shape[0]
     h, w = int(frames.shape[1]), int(frames.shape[2])
     size = net_input_size(h, w, input_size)
     nwin = len(window_starts(n))
     rounds = (nwin + world - 1) // world
-    dev = torch.device(device)
     on_device = stitch == "device"
     out_hw = size if on_device else (h, w)  # the size a window has when it reaches the sink / the gather
     sink = None
     if rank == 0:
         sink = _DeviceSink(dev, n, (h, w), align, return_device) if on_device else _HostSink(dev, n)
-    source = _HostSource(frames, dev)
+    source = _HostSource(frames, dev) if planar is None else _PlanarSource(planar, dev)
     wpb = max(1, int(windows_per_batch))
     if prepare is None and callable(getattr(forward, "prepare", None)):  # the model itself as the forward
         prepare = lambda hw: forward.prepare(dev, hw)  # noqa: E731
@@ -598,7 +644,8 @@ def infer_video_depth(forward: Callable[[torch.Tensor], torch.Tensor], frames, t
             if ks:
                 idx = [window_frame_indices(k, n) for k in ks]
                 uniq = sorted(set(i for row in idx for i in row))
-                pre = io.preprocess(source.get(uniq), size)
+                pre = (io.preprocess(source.get(uniq), size) if planar is None
+                       else io.preprocess_planar(source.get(uniq), planar, size))
                 pos = {f: j for j, f in enumerate(uniq)}
                 x = torch.stack([pre[[pos[i] for i in row]] for row in idx], 0)
                 del pre

@@ -11,6 +11,9 @@ and encoders that need only numpy / Pillow:
   (.mp4 ...) go through decord when it is importable.  Frame stride = max(round(source_fps / target_fps), 1); at most
   ``process_length`` frames; ``max_res`` scales the longer side down (decord branch: sizes rounded
   and made even, dc_utils.py:22-29).
+* ``open_y4m(path, process_length, target_fps) -> (Y4MFrames, fps)``: a ``.y4m`` file indexed and memory-mapped
+  but not decoded, with the same frame selection.  ``Y4MFrames.payload`` hands out the planar YUV bytes of frames
+  (what ``infer_video_depth`` uploads on a GPU, vda_amd.decode), ``rgb`` / ``np.asarray`` decode as ``read_y4m``.
 * ``save_video(frames, path, fps, is_depths, grayscale, spectral)`` (dc_utils.py:72-89): depth is
   min/max-normalised to uint8 over the whole clip and mapped through matplotlib's inferno (or
   Spectral) table; written as ``.y4m`` (4:4:4), or animated GIF / PNG / WebP via Pillow; ``.mp4``
@@ -24,7 +27,7 @@ of the reference's decord path are therefore parity-unpinned here (no decoder to
 from __future__ import annotations
 
 import os
-from typing import Tuple
+from typing import Optional, Tuple
 
 import numpy as np
 
@@ -62,12 +65,29 @@ def _parse_ratio(s: str) -> float:
     return float(a) / float(b) if float(b) else 0.0
 
 
-def read_y4m(path: str) -> Tuple[np.ndarray, float]:
-    """All frames of a YUV4MPEG2 file as RGB uint8 [N, h, w, 3], plus its frame rate."""
-    with open(path, "rb") as f:
-        data = f.read()
-    nl = data.index(b"\n")
-    head = data[:nl].decode("ascii").split()
+def _decode_payload(buf: np.ndarray, w: int, h: int, cw: int, ch: int) -> np.ndarray:
+    """One frame's planar payload (Y, then U and V of ch x cw) -> RGB uint8 [h, w, 3], chroma taken nearest."""
+    y = buf[:w * h].reshape(h, w)
+    if cw == 0:
+        u = v = np.full((h, w), 128, np.uint8)
+    else:
+        u = buf[w * h:w * h + cw * ch].reshape(ch, cw)
+        v = buf[w * h + cw * ch:w * h + 2 * cw * ch].reshape(ch, cw)
+        ry, rx = (2 if ch != h else 1), (2 if cw != w else 1)  # nearest chroma upsampling
+        u = np.repeat(np.repeat(u, ry, 0), rx, 1)[:h, :w]
+        v = np.repeat(np.repeat(v, ry, 0), rx, 1)[:h, :w]
+    return _yuv_to_rgb(y, u, v)
+
+
+def _y4m_stream_header(data, path: str, refuse_depth_suffix: bool = False):
+    """The stream header of a YUV4MPEG2 file (bytes or a memory map) -> (w, h, fps, cw, ch, "420" / "422" /
+    "444" / "mono", offset of the first frame header); 8-bit 420 / 422 / 444 / mono only.  ``read_y4m`` takes
+    a ``p<bits>`` suffix (C420p10) for a siting tag (C420paldv) and fails at the first frame header instead;
+    ``refuse_depth_suffix`` refuses it here."""
+    nl = data.find(b"\n")
+    if nl < 0:
+        raise ValueError(f"{path}: not a YUV4MPEG2 stream")
+    head = bytes(data[:nl]).decode("ascii").split()
     if not head or head[0] != "YUV4MPEG2":
         raise ValueError(f"{path}: not a YUV4MPEG2 stream")
     w = h = None
@@ -85,6 +105,8 @@ def read_y4m(path: str) -> Tuple[np.ndarray, float]:
     if w is None or h is None:
         raise ValueError(f"{path}: y4m header lacks W/H")
     base = cs.split("p")[0]
+    if refuse_depth_suffix and cs[len(base):].startswith("p") and cs[len(base) + 1:].isdigit():
+        base = ""  # a bit depth, not a siting tag: refused below
     if base.startswith("420"):
         cw, ch = (w + 1) // 2, (h + 1) // 2
     elif base == "422":
@@ -95,9 +117,16 @@ def read_y4m(path: str) -> Tuple[np.ndarray, float]:
         cw = ch = 0
     else:
         raise ValueError(f"{path}: unsupported y4m colourspace C{cs} (8-bit 420/422/444/mono only)")
+    return w, h, fps, cw, ch, ("420" if base.startswith("420") else base), nl + 1
+
+
+def read_y4m(path: str) -> Tuple[np.ndarray, float]:
+    """All frames of a YUV4MPEG2 file as RGB uint8 [N, h, w, 3], plus its frame rate."""
+    with open(path, "rb") as f:
+        data = f.read()
+    w, h, fps, cw, ch, _, pos = _y4m_stream_header(data, path)
     fsz = w * h + 2 * cw * ch
     frames = []
-    pos = nl + 1
     while pos < len(data):
         e = data.index(b"\n", pos)
         if not data[pos:e].startswith(b"FRAME"):
@@ -105,19 +134,89 @@ def read_y4m(path: str) -> Tuple[np.ndarray, float]:
         pos = e + 1
         buf = np.frombuffer(data, np.uint8, fsz, pos)
         pos += fsz
-        y = buf[:w * h].reshape(h, w)
-        if cw == 0:
-            u = v = np.full((h, w), 128, np.uint8)
-        else:
-            u = buf[w * h:w * h + cw * ch].reshape(ch, cw)
-            v = buf[w * h + cw * ch:].reshape(ch, cw)
-            ry, rx = (2 if ch != h else 1), (2 if cw != w else 1)  # nearest chroma upsampling
-            u = np.repeat(np.repeat(u, ry, 0), rx, 1)[:h, :w]
-            v = np.repeat(np.repeat(v, ry, 0), rx, 1)[:h, :w]
-        frames.append(_yuv_to_rgb(y, u, v))
+        frames.append(_decode_payload(buf, w, h, cw, ch))
     if not frames:
         return np.zeros((0, h, w, 3), np.uint8), fps
     return np.stack(frames), fps
+
+
+class Y4MFrames:
+    """The frames of a YUV4MPEG2 file, indexed but not decoded (``open_y4m``).  The file is memory-mapped;
+    ``payload`` hands out the planar YUV bytes of frames as they lie in the file (what vda_amd.decode's
+    kernels take), ``rgb`` / ``np.asarray`` decode on the host as ``read_y4m`` does, so anything that wants
+    RGB frames takes this object too.  ``shape`` is that of the RGB frames, ``(N, h, w, 3)``."""
+
+    def __init__(self, path: str, data, offsets, w: int, h: int, cw: int, ch: int, chroma: str):
+        self.path = path
+        self.data = data                              # uint8 view of the whole file
+        self.offsets = np.asarray(offsets, np.int64)  # byte offset of each selected frame's payload
+        self.w, self.h, self.cw, self.ch = int(w), int(h), int(cw), int(ch)
+        self.chroma = chroma                          # "420", "422", "444" or "mono"
+        self.payload_bytes = self.w * self.h + 2 * self.cw * self.ch
+        self.frame_stride = (self.payload_bytes + 15) // 16 * 16  # frames of a payload block are padded to this
+
+    @property
+    def shape(self) -> tuple:
+        return (len(self.offsets), self.h, self.w, 3)
+
+    def __len__(self) -> int:
+        return len(self.offsets)
+
+    def payload(self, indices, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """The planar bytes of frames ``indices`` as uint8 [n, frame_stride] (into ``out`` when given); the
+        padding bytes of a row are not written."""
+        idx = [int(i) for i in indices]
+        if out is None:
+            out = np.zeros((len(idx), self.frame_stride), np.uint8)
+        if out.shape != (len(idx), self.frame_stride) or out.dtype != np.uint8:
+            raise ValueError(f"out must be uint8 {(len(idx), self.frame_stride)}, got {out.dtype} {out.shape}")
+        n = self.payload_bytes
+        for j, i in enumerate(idx):
+            o = int(self.offsets[i])
+            out[j, :n] = self.data[o:o + n]
+        return out
+
+    def rgb(self, indices=None) -> np.ndarray:
+        """Frames ``indices`` (default: all) decoded on the host: uint8 [n, h, w, 3], equal to ``read_y4m``."""
+        idx = range(len(self)) if indices is None else [int(i) for i in indices]
+        out = np.zeros((len(idx), self.h, self.w, 3), np.uint8)
+        for j, i in enumerate(idx):
+            o = int(self.offsets[i])
+            out[j] = _decode_payload(self.data[o:o + self.payload_bytes], self.w, self.h, self.cw, self.ch)
+        return out
+
+    def __array__(self, dtype=None, copy=None):
+        a = self.rgb()
+        return a if dtype is None else a.astype(dtype, copy=False)
+
+
+def open_y4m(path: str, process_length: int = -1, target_fps: float = -1) -> Tuple[Y4MFrames, float]:
+    """Index a YUV4MPEG2 file without decoding it: ``(Y4MFrames, fps)`` with ``read_video_frames``' frame
+    selection (stride = max(round(source_fps / target_fps), 1), at most ``process_length`` frames).  The
+    stream header is parsed and refused as ``read_y4m`` does; the FRAME headers are walked once, since they
+    may carry parameters and the payloads are therefore not a fixed stride apart."""
+    import mmap
+    with open(path, "rb") as f:
+        mm = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
+    w, h, src_fps, cw, ch, chroma, pos = _y4m_stream_header(mm, path, refuse_depth_suffix=True)
+    fsz = w * h + 2 * cw * ch
+    offsets = []
+    size = len(mm)
+    while pos < size:
+        e = mm.find(b"\n", pos)
+        if e < 0 or mm[pos:pos + 5] != b"FRAME":
+            raise ValueError(f"{path}: corrupt frame header at byte {pos}")
+        pos = e + 1
+        if pos + fsz > size:
+            raise ValueError(f"{path}: truncated frame at byte {pos} ({size - pos} of {fsz} bytes)")
+        offsets.append(pos)
+        pos += fsz
+    fps = src_fps if target_fps == -1 else target_fps
+    idx = list(range(0, len(offsets), max(round(src_fps / fps), 1)))
+    if process_length != -1 and process_length < len(idx):
+        idx = idx[:process_length]
+    data = np.frombuffer(mm, np.uint8)
+    return Y4MFrames(path, data, [offsets[i] for i in idx], w, h, cw, ch, chroma), fps
 
 
 def _subsample_420(p: np.ndarray) -> np.ndarray:
