@@ -175,8 +175,12 @@ int vda_row_stats(const void* x, int64_t ldx, float* stats, int32_t rows, int32_
  * GroupNorm over NHWC frames: X [F, S, C] half -> Y [F, S, C] half, `groups` groups of C/groups
  * channels, statistics over (S x C/groups) in fp32.  `ws`: a float workspace of
  * vda_groupnorm_workspace(F, S, C, groups) entries enables the three-pass coalesced path
- * (per-chunk partial sums around a per-group shift, finalize, apply; deterministic); NULL runs the
- * one-block-per-(frame, group) kernel.  Replaces motion_module.py:116 (GroupNorm(32, eps 1e-6)).
+ * (per row-chunk and channel the mean and the centred second moment, two-pass from registers; their
+ * parallel-variance merge per (frame, group); apply; deterministic); NULL runs the
+ * one-block-per-(frame, group) two-pass kernel.  Both take every second moment about the mean of the
+ * values it sums, so a massive activation anywhere in the frame cannot cancel the variance.  The
+ * workspace holds no input: the call writes all of it that it reads.
+ * Replaces motion_module.py:116 (GroupNorm(32, eps 1e-6)).
  */
 int vda_groupnorm(const void* x, void* y, const float* gamma, const float* beta, int32_t F,
                   int32_t S, int32_t C, int32_t groups, float eps, float* ws, void* stream);

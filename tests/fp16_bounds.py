@@ -1,7 +1,7 @@
 """Float64 references, derived per-element error bounds and CPU emulations for the fp16 kernels.
 
 Shared by tests/test_fp16_bounds.py (CPU: every emulation lies inside its bound) and
-tests/test_gpu_fp16_edges.py (GPU: every kernel output lies inside the same bound); DESIGN.md
+tests/test_gpu_fp16_edges.py / tests/test_gpu_fp16_small_ops.py (GPU: every kernel output lies inside the same bound); DESIGN.md
 "Per-element bounds of the fp16 kernels" has the derivation in prose.
 
 Every `*_ref_bound` takes tensors whose VALUES are already fp16-representable (fp32 for bias / gamma /
@@ -579,3 +579,606 @@ def gemm_ln_case(M, N, K, kind, seed=0, eps=1e-6):
     elif kind == "ln_rowbias":  # the motion modules' per-frame PE row bias (EK 3): rdiv >= 256
         c["kw"].update(rowbias=torch.randn(3, N, generator=g), rdiv=300, rmod=3)
     return c
+
+
+# =====================================================================================================
+# LayerNorm, GroupNorm, GroupNorm -> Linear (csrc/vda_norm.hip)
+# =====================================================================================================
+def fma32(a, b, c):
+    """fp32 fma(a, b, c) on fp32 tensors: the product is exact in float64 (24 + 24 bits), the sum rounds to
+    float64 and then to fp32 (a double rounding differs from the fused one only on a 2^-29 tie window)."""
+    return (a.double() * b.double() + c.double()).float()
+
+
+def wave_tree(v):
+    """wave_sum (vda_common.h:140): the xor butterfly 32, 16, .. 1 over the last dim (any power of two <= 64);
+    every lane ends with the same bits, lane 0 is returned."""
+    n = v.shape[-1]
+    idx = torch.arange(n)
+    o = n // 2
+    while o:
+        v = v + v[..., idx ^ o]
+        o //= 2
+    return v[..., 0]
+
+
+def _norm_out(x, mean, rstd, g, b, dmean, dvar, eps):
+    """y = (x - mean) * rstd * g + b in float64 and its bound when the kernel's mean is within dmean and its
+    variance within dvar: rstd~ / rstd - 1 is within drel = r / (2 (1 - r)) + 4 u32, r = dvar / (var + eps) (the
+    add of eps, the division by n, v_rsq_f32 at 1 ulp); (x - mean~) sc~ = ((x - mean) + (mean - mean~)) sc
+    (1 + drel); the kernels evaluate either ((x - mean) * rstd) * g + b or fma(x, sc, fma(-mean, sc, b)): at most
+    four fp32 roundings, each relative to a partial result <= A = |sc| (|x| + |mean|) + |b|; one fp16 store."""
+    var_eps = rstd ** -2
+    r = (dvar / var_eps).clamp_max(0.5)
+    drel = 0.5 * r / (1 - r) + 4 * U32
+    sc = rstd * g
+    v = (x - mean) * sc
+    ref = v + b
+    A = sc.abs() * (x.abs() + mean.abs()) + b.abs()
+    bound = U16 * ref.abs() + sc.abs() * dmean * (1 + drel) + drel * v.abs() + 4 * U32 * A + SUB16
+    return ref, bound, drel
+
+
+def ln_depth(C):
+    """Summation depth of the LayerNorm kernels' statistics: 8 values per 16-byte chunk, ceil(C / 512) chunks per
+    lane in sequence (layernorm_kernel, vda_norm.hip:21-31; one in layernorm_narrow_kernel :136), then the
+    6-level wave tree (:32, log2(LPR) levels in the narrow kernel :138)."""
+    return 8 * ((C // 8 + 63) // 64) + 6
+
+
+def _ln_stats(x, eps):
+    C = x.shape[1]
+    D = ln_depth(C)
+    mean = x.mean(1, keepdim=True)
+    var = ((x - mean) ** 2).mean(1, keepdim=True)
+    dmean = gam(D + 1) * x.abs().mean(1, keepdim=True)  # D adds and the division by C
+    # sum (x - mean~)^2 = sum (x - mean)^2 + C (mean~ - mean)^2 exactly; each term rounds d and d * d, the sum D
+    # times, the division once
+    dvar = gam(D + 4) * (var + dmean ** 2) + dmean ** 2
+    return mean, var, dmean, dvar
+
+
+def layernorm_ref_bound(x, g, b, eps):
+    """layernorm_kernel / layernorm_narrow_kernel<16|32|64> (vda_norm.hip:8-59, :122-155): two-pass fp32
+    statistics from registers over the fp16 row, then fp16((v - mean) * rstd * g + b) (:53, :151), the ONLY fp16
+    rounding.  x [R, C] (fp16 values), g / b [C] fp32.  Bound: half an fp16 ulp of the reference + the fp32
+    terms of _norm_out + the statistics term of _ln_stats at the kernel's summation depth ln_depth(C)."""
+    x, g, b = map(d, (x, g, b))
+    mean, var, dmean, dvar = _ln_stats(x, eps)
+    ref, bound, _ = _norm_out(x, mean, (var + eps) ** -0.5, g[None], b[None], dmean, dvar, eps)
+    return ref, bound
+
+
+def ln_stats_ref_bound(x, eps):
+    """row_stats_kernel (vda_norm.hip:63-96): (mean, rstd) per row [R, 2] fp32 from the same two passes: mean
+    within dmean + u32 |mean|, rstd within rstd * drel (_norm_out)."""
+    x = d(x)
+    mean, var, dmean, dvar = _ln_stats(x, eps)
+    rstd = (var + eps) ** -0.5
+    one = torch.ones_like(mean)
+    _, _, drel = _norm_out(x[:, :1], mean, rstd, one, one, dmean, dvar, eps)
+    ref = torch.cat([mean, rstd], 1)
+    return ref, torch.cat([dmean + U32 * mean.abs() + 2.0 ** -140, rstd * drel], 1)
+
+
+def emulate_layernorm(x, g, b, eps, stats_only=False, drop_lane=None):
+    """The kernels' order: lane l sums chunks l, l + 64, .. (8 values each, in order), the wave tree, mean = s / C;
+    q = fma(d, d, q) in the same order (hipcc contracts q += d * d), rstd = rsqrt(q / C + eps);
+    y = fp16(fma((v - mean) * rstd, g, b)).  A narrow row (C / 8 lanes) is the same sums with the other lanes at
+    zero.  drop_lane: a MUTANT that leaves one lane out of both reductions (test_fp16_bounds.py only)."""
+    x, g, b = (t.detach().to("cpu", torch.float32) for t in (x, g, b))
+    R, C = x.shape
+    xp = F.pad(x, (0, 2048 - C)).view(R, 4, 64, 8)
+    live = (torch.arange(2048) < C).view(4, 64, 8)
+    if drop_lane is not None:
+        live = live.clone()
+        live[:, drop_lane] = False
+    s = torch.zeros(R, 64)
+    for i in range(4):
+        for j in range(8):
+            s = torch.where(live[i, :, j], s + xp[:, i, :, j], s)
+    mean = wave_tree(s) / float(C)
+    q = torch.zeros(R, 64)
+    for i in range(4):
+        for j in range(8):
+            dd = xp[:, i, :, j] - mean[:, None]
+            q = torch.where(live[i, :, j], fma32(dd, dd, q), q)
+    rstd = torch.rsqrt(wave_tree(q) / float(C) + torch.tensor(eps, dtype=torch.float32))
+    if stats_only:
+        return torch.stack([mean, rstd], 1)
+    return fma32((x - mean[:, None]) * rstd[:, None], g[None].expand_as(x), b[None].expand_as(x)).half()
+
+
+LN_CS = [8, 64, 128, 256, 384, 512, 520, 1024, 2040, 2048]
+
+
+def ln_rows(R, C, seed=0):
+    """R random rows, then the stress rows: a +1000 offset, one 60000 outlier, a constant row, an all-zero row."""
+    x = rnd16(R + 4, C, seed=seed + R + C) * 2 + 0.5
+    x[R] += 1000.0
+    x[R + 1, C // 3] = 60000.0
+    x[R + 2] = 3.0
+    x[R + 3] = 0.0
+    return x.half().float()
+
+
+def gn_rows(C):
+    return 32 if C >= 512 else 128
+
+
+def gn_layout(C):
+    """(cpr, rpi, nr) of gn_partial / gn_apply (vda_norm.hip gn_layout, gn_stats_launch): 16-byte chunks per row,
+    row-lanes of a 256-thread block, rows per thread."""
+    cpr = C // 8
+    rpi = 256 // cpr
+    return cpr, rpi, (gn_rows(C) + rpi - 1) // rpi
+
+
+def gn_depth(S, C, groups):
+    """The deeper of the two routes' summation depths.  groupnorm_kernel<VW> (vda_norm.hip:181-196): ceil(S cg /
+    (256 VW)) vectors of VW values per thread in sequence, the wave tree (6) and the four waves (3).  Workspace
+    route: nr rows per thread, the rpi row-lanes folded in sequence (gn_partial_kernel), then ceil(nchunk cg / 64)
+    pairs per lane in sequence and the wave tree, with the merge's own products (gn_finalize_kernel)."""
+    cg = C // groups
+    vw = 8 if cg % 8 == 0 else 4 if cg % 4 == 0 else 2
+    two_pass = -(-(S * cg // vw) // 256) * vw + 9
+    if C % 8 or C > 2048:
+        return two_pass
+    _, rpi, nr = gn_layout(C)
+    nchunk = -(-S // gn_rows(C))
+    return max(two_pass, nr + rpi + -(-nchunk * cg // 64) + 6 + 4)
+
+
+def _gn_stats(x, groups, eps):
+    """x [F, S, C] float64 -> per (frame, group) mean, var, dmean, dvar [F, 1, groups, 1].
+
+    The statistics term is that of a two-pass fp32 variance, in a form that also covers the merge of chunk-local
+    two-pass moments: with D = gn_depth and rms^2 = var + mean^2 (the data's spread about zero),
+        dmean = gamma(D) rms                     (a D-deep fp32 sum of n values: gamma(D) mean|x| <= gamma(D) rms)
+        dvar  = gamma(D) (var + dmean^2) + dmean^2 + 2 sqrt(var) dmean
+    The first two terms are the two-pass kernel's (sum (x - m~)^2 = n var + n (m~ - m)^2 exactly).  The last is
+    the merged form's: n var = sum_i M2_i + n_i (m_i - m)^2 over chunks i, whose computed chunk means m~_i = m_i +
+    e_i, |e_i| <= gamma(D) rms_i, enter the between-chunk term to first order, 2 sum n_i (m_i - m) e_i <= 2 n
+    sqrt(var) gamma(D) rms (Cauchy-Schwarz, sum n_i rms_i^2 = n rms^2).  It depends on n = S cg (through D) and on
+    var and mean only: NOT on where in the frame any value lies, so it cannot absorb a cancellation that comes
+    from a value's position (the first-value shift of the one-pass variance this route used before)."""
+    Fr, S, C = x.shape
+    xg = x.view(Fr, S, groups, C // groups)
+    mean = xg.mean((1, 3), keepdim=True)
+    var = ((xg - mean) ** 2).mean((1, 3), keepdim=True)
+    D = gn_depth(S, C, groups)
+    dmean = gam(D) * (var + mean ** 2).sqrt()
+    dvar = gam(D) * (var + dmean ** 2) + dmean ** 2 + 2 * var.sqrt() * dmean
+    return xg, mean, var, dmean, dvar
+
+
+def groupnorm_ref_bound(x, g, b, groups, eps):
+    """GroupNorm of x [F, S, C] (fp16 values) over (S, C / groups) per frame and group -> (ref, bound) [F, S, C].
+    Both routes (groupnorm_kernel<8|4|2>, vda_norm.hip:160-208; gn_partial / gn_finalize / gn_apply) keep fp32 up
+    to the one fp16 store (:204; gn_apply's fp16(fma(x, sc, of))): half an fp16 ulp + the fp32 terms of _norm_out
+    + the statistics term of _gn_stats."""
+    x, g, b = map(d, (x, g, b))
+    Fr, S, C = x.shape
+    xg, mean, var, dmean, dvar = _gn_stats(x, groups, eps)
+    gg, bb = g.view(1, 1, groups, -1), b.view(1, 1, groups, -1)
+    ref, bound, _ = _norm_out(xg, mean, (var + eps) ** -0.5, gg, bb, dmean, dvar, eps)
+    return ref.reshape(Fr, S, C), bound.reshape(Fr, S, C)
+
+
+def gn_stats_ref_bound(x, groups, eps):
+    """(mean, rstd) per (frame, group) [F, groups, 2] and their bound (for the emulations' statistics)."""
+    x = d(x)
+    xg, mean, var, dmean, dvar = _gn_stats(x, groups, eps)
+    rstd = (var + eps) ** -0.5
+    one = torch.ones_like(mean)
+    _, _, drel = _norm_out(mean, mean, rstd, one, one, dmean, dvar, eps)
+    f = lambda t: t.reshape(x.shape[0], groups)  # noqa: E731
+    return torch.stack([f(mean), f(rstd)], -1), torch.stack([f(dmean + U32 * mean.abs()) + 2.0 ** -140, f(rstd * drel)], -1)
+
+
+def emulate_groupnorm_two_pass(x, g, b, groups, eps):
+    """groupnorm_kernel<VW>: thread t of the (frame, group) block sums vectors t, t + 256, .. of the [S, cg] slab
+    (VW values each, in order), wave tree, red[0] + red[1] + red[2] + red[3]; mean = s / n; the same order for
+    q += d * d (contracted to an fma); y = fp16(fma((v - mean) * rstd, g, b))."""
+    x, g, b = (t.detach().to("cpu", torch.float32) for t in (x, g, b))
+    Fr, S, C = x.shape
+    cg = C // groups
+    vw = 8 if cg % 8 == 0 else 4 if cg % 4 == 0 else 2
+    n = S * cg
+    it = -(-n // (256 * vw))
+    flat = x.view(Fr, S, groups, cg).permute(0, 2, 1, 3).reshape(Fr * groups, n)
+    xp = F.pad(flat, (0, it * 256 * vw - n)).view(-1, it, 256, vw)
+    live = (torch.arange(it * 256 * vw) < n).view(it, 256, vw)
+
+    def block_sum(term):
+        s = torch.zeros(xp.shape[0], 256)
+        for i in range(it):
+            for j in range(vw):
+                s = torch.where(live[i, :, j], term(s, xp[:, i, :, j]), s)
+        w = wave_tree(s.view(-1, 4, 64))
+        return ((w[:, 0] + w[:, 1]) + w[:, 2]) + w[:, 3]
+    cnt = float(S) * float(cg)
+    mean = block_sum(lambda s, v: s + v) / cnt
+    q = block_sum(lambda s, v: fma32(v - mean[:, None], v - mean[:, None], s))
+    rstd = torch.rsqrt(q / cnt + torch.tensor(eps, dtype=torch.float32))
+    mean, rstd = mean.view(Fr, 1, groups, 1), rstd.view(Fr, 1, groups, 1)
+    xg = x.view(Fr, S, groups, cg)
+    gg, bb = g.view(1, 1, groups, cg).expand_as(xg), b.view(1, 1, groups, cg).expand_as(xg)
+    return fma32((xg - mean) * rstd, gg, bb).half().view(Fr, S, C)
+
+
+def _gn_chunks(x):
+    """x [F, S, C] fp32 -> (xc [F, nchunk, nr, rpi, C] zero-padded, live [nchunk, nr, rpi] bool, rows [nchunk]):
+    thread (row-lane q, chunk column) of block (frame, chunk) owns rows chunk * gn_rows + q + i * rpi, i < nr."""
+    Fr, S, C = x.shape
+    _, rpi, nr = gn_layout(C)
+    R = gn_rows(C)
+    nchunk = -(-S // R)
+    xs = F.pad(x, (0, 0, 0, nchunk * R - S)).view(Fr, nchunk, R, C)
+    xc = F.pad(xs, (0, 0, 0, nr * rpi - R)).view(Fr, nchunk, nr, rpi, C)
+    local = torch.arange(nr * rpi).view(1, nr, rpi)
+    rows = (S - torch.arange(nchunk) * R).clamp_max(R)
+    live = local < rows.view(-1, 1, 1)
+    return xc, live, rows
+
+
+def _gn_apply(x, mean, rstd, g, b, groups, chunk_group=False):
+    """gn_apply_kernel (vda_norm.hip): sc = rstd * g, of = fma(-mean, sc, b), y = fp16(fma(x, sc, of)), the group
+    looked up per CHANNEL.  chunk_group=True: a MUTANT that takes the group of its 8-channel chunk's first channel
+    for all eight (wrong wherever a chunk spans two groups, cg = 2, 4, 6, 12; test_fp16_bounds.py only)."""
+    Fr, S, C = x.shape
+    cg = C // groups
+    ch = torch.arange(C)
+    grp = (ch // 8 * 8 if chunk_group else ch) // cg
+    mc, rc = mean[:, grp].view(Fr, 1, C), rstd[:, grp].view(Fr, 1, C)
+    sc = rc * g.view(1, 1, C)
+    of = fma32(-mc, sc, b.view(1, 1, C).expand_as(sc))
+    return fma32(x, sc.expand_as(x), of.expand_as(x)).half()
+
+
+def _gn_finalize_lanes(vals, groups):
+    """[F, nchunk, C] -> [F, groups, 64 lanes, per-lane sequence]: entry i = chunk * cg + channel of the group goes
+    to lane i % 64, step i / 64 (gn_finalize_kernel's loop); also returns the live mask of the padded steps."""
+    Fr, nchunk, C = vals.shape
+    cg = C // groups
+    n = nchunk * cg
+    steps = -(-n // 64)
+    v = vals.view(Fr, nchunk, groups, cg).permute(0, 2, 1, 3).reshape(Fr, groups, n)
+    v = F.pad(v, (0, steps * 64 - n)).view(Fr, groups, steps, 64)
+    return v, (torch.arange(steps * 64) < n).view(steps, 64)
+
+
+def emulate_groupnorm_ws(x, g, b, groups, eps, stats_only=False, chunk_group=False):
+    """gn_partial_kernel / gn_finalize_kernel / gn_apply_kernel as they stand: per (frame, chunk) block each
+    thread sums its nr rows per channel, the rpi row-lanes are folded in order, chunk mean = sum * (1 / rows);
+    M2 = fma(d, d, M2) with d = x - chunk mean in the same order and fold; gn_finalize: lane i % 64 takes pair i,
+    a1 = fma(rows, mean_i, a1), wave tree, mean = a1 / n; a2 += fma(rows * d, d, M2_i), wave tree,
+    rstd = rsqrt(a2 / n + eps)."""
+    x, g, b = (t.detach().to("cpu", torch.float32) for t in (x, g, b))
+    Fr, S, C = x.shape
+    cg = C // groups
+    xc, live, rows = _gn_chunks(x)
+    nchunk, nr, rpi = live.shape
+
+    def fold(term):
+        s = torch.zeros(Fr, nchunk, rpi, C)
+        for i in range(nr):
+            s = torch.where(live[None, :, i, :, None], term(s, xc[:, :, i]), s)
+        a = torch.zeros(Fr, nchunk, C)
+        for q in range(rpi):
+            a = a + s[:, :, q]
+        return a
+    rowsf = rows.float()
+    cm = fold(lambda s, v: s + v) * (1.0 / rowsf).view(1, -1, 1)
+    m2 = fold(lambda s, v: fma32(v - cm[:, :, None], v - cm[:, :, None], s))
+    cnt = float(S) * float(cg)
+    rw = rowsf.view(1, -1, 1).expand(Fr, nchunk, C).contiguous()
+    mv, lv = _gn_finalize_lanes(cm, groups)
+    rv, _ = _gn_finalize_lanes(rw, groups)
+    m2v, _ = _gn_finalize_lanes(m2, groups)
+    a1 = torch.zeros(Fr, groups, 64)
+    for s_ in range(mv.shape[2]):
+        a1 = torch.where(lv[s_], fma32(rv[:, :, s_], mv[:, :, s_], a1), a1)
+    mean = wave_tree(a1) / cnt
+    a2 = torch.zeros(Fr, groups, 64)
+    for s_ in range(mv.shape[2]):
+        dd = mv[:, :, s_] - mean[..., None]
+        a2 = torch.where(lv[s_], a2 + fma32(rv[:, :, s_] * dd, dd, m2v[:, :, s_]), a2)
+    rstd = torch.rsqrt(wave_tree(a2) / cnt + torch.tensor(eps, dtype=torch.float32))
+    if stats_only:
+        return torch.stack([mean, rstd], -1)
+    return _gn_apply(x, mean, rstd, g, b, groups, chunk_group)
+
+
+def emulate_groupnorm_ws_first_value_shift(x, g, b, groups, eps, stats_only=False):
+    """The workspace route AS IT WAS before its repair (kept as the evidence that groupnorm_ref_bound has teeth):
+    gn_partial summed d and fma(d, d, .) with d = x - shift, shift = x[f, 0, group's first channel], in the same
+    thread / fold order; gn_finalize summed the pairs per lane and the wave tree, md = a1 / n,
+    var = max(a2 / n - md * md, 0), mean = shift + md.  An outlier AT the shift position makes a2 / n and md^2 both
+    ~ v0^2 and the variance their difference."""
+    x, g, b = (t.detach().to("cpu", torch.float32) for t in (x, g, b))
+    Fr, S, C = x.shape
+    cg = C // groups
+    xc, live, rows = _gn_chunks(x)
+    nchunk, nr, rpi = live.shape
+    sh = x[:, 0].view(Fr, groups, cg)[:, :, :1].expand(Fr, groups, cg).reshape(Fr, 1, 1, C)
+
+    def fold(term):
+        s = torch.zeros(Fr, nchunk, rpi, C)
+        for i in range(nr):
+            s = torch.where(live[None, :, i, :, None], term(s, xc[:, :, i] - sh), s)
+        a = torch.zeros(Fr, nchunk, C)
+        for q in range(rpi):
+            a = a + s[:, :, q]
+        return a
+    p1, lv = _gn_finalize_lanes(fold(lambda s, dd: s + dd), groups)
+    p2, _ = _gn_finalize_lanes(fold(lambda s, dd: fma32(dd, dd, s)), groups)
+    a1, a2 = torch.zeros(Fr, groups, 64), torch.zeros(Fr, groups, 64)
+    for s_ in range(p1.shape[2]):
+        a1 = torch.where(lv[s_], a1 + p1[:, :, s_], a1)
+        a2 = torch.where(lv[s_], a2 + p2[:, :, s_], a2)
+    cnt = float(S) * float(cg)
+    md = wave_tree(a1) / cnt
+    var = fma32(-md, md, wave_tree(a2) / cnt).clamp_min(0)
+    mean = sh.view(Fr, groups, cg)[:, :, 0] + md
+    rstd = torch.rsqrt(var + torch.tensor(eps, dtype=torch.float32))
+    if stats_only:
+        return torch.stack([mean, rstd], -1)
+    return _gn_apply(x, mean, rstd, g, b, groups)
+
+
+def groupnorm_linear_ref_bound(x, g, b, groups, eps, w, bias=None):
+    """GroupNorm -> Linear, y = GN(x) w^T + bias on x [F, S, C], w [N, C] (fp16 values) -> (ref, bound) [F S, N].
+    gn_linear_kernel<64|128|256> (vda_norm.hip) multiplies gn_apply's fp16 operand z (the kernel forms the very
+    bits of fp16(fma(x, sc, of))), accumulates the K = C products in fp32 MFMAs, adds the bias in fp32 and
+    rounds once to fp16; the unfused route is the same operand through vda_gemm.  |z - GN64(x)| <= bz, the
+    GroupNorm bound, reaches the output through |w| in the worst case (every operand error with the sign of its
+    weight): bound = u16 |ref| + bz |w|^T + gamma(K + 1) ((|GN64| + bz) |w|^T + |bias|) + 2^-24."""
+    zr, bz = groupnorm_ref_bound(x, g, b, groups, eps)
+    w, bias = d(w), d(bias)
+    K = w.shape[1]
+    zr, bz = zr.reshape(-1, K), bz.reshape(-1, K)
+    ref, A, dz = zr @ w.t(), (zr.abs() + bz) @ w.abs().t(), bz @ w.abs().t()
+    if bias is not None:
+        ref, A = ref + bias, A + bias.abs()
+    return ref, U16 * ref.abs() + dz + gam(K + 1) * A + SUB16
+
+
+def emulate_groupnorm_linear(x, g, b, groups, eps, w, bias=None, drop=None):
+    """drop=(k0, k1): a MUTANT that leaves the K range [k0, k1) out of rows m % 16 == 5 (one lane group's k-step)."""
+    z = emulate_groupnorm_ws(x, g, b, groups, eps).float().view(-1, x.shape[-1])
+    w = w.detach().to("cpu", torch.float32)
+    v = z @ w.t()
+    if drop is not None:
+        rows = torch.arange(z.shape[0]) % 16 == 5
+        v[rows] -= z[rows, drop[0]:drop[1]] @ w[:, drop[0]:drop[1]].t()
+    if bias is not None:
+        v = v + bias.detach().to("cpu", torch.float32)
+    return v.half()
+
+
+def sums_ref_bound(y16):
+    """(sum, sum of squares) of each stored fp16 row [M, N] -> [M, 2] float64 and the bound of an N-term fp32 sum
+    in any order with the squares' roundings (gn_linear_kernel's stats_out: N / 4 per lane, then the lane groups)."""
+    y = d(y16)
+    n = y.shape[1]
+    ref = torch.stack([y.sum(-1), (y * y).sum(-1)], -1)
+    return ref, gam(n + 8) * torch.stack([y.abs().sum(-1), (y * y).sum(-1)], -1) + 2.0 ** -100
+
+
+def gn_input(Fr, S, C, seed=0, sigma=1.0, mu=0.3):
+    g = torch.Generator().manual_seed(seed)
+    return (torch.randn(Fr, S, C, generator=g) * sigma + mu).half().float()
+
+
+def gn_affine(C, seed=0):
+    return rnd32(C, scale=0.1, seed=seed + 11) + 1, rnd32(C, scale=0.1, seed=seed + 12)
+
+
+# (C, groups): cg = 2, 4, 6, 8, 12, 32, 64; C = 24 / 48: 3 / 6 chunks per row leave idle threads in gn_layout;
+# C = 2048: one row-lane (rpi = 1).  S around both gn_rows values (128 below C = 512, 32 from there).
+GN_SHAPES = [(64, 32), (128, 32), (24, 4), (256, 32), (48, 4), (1024, 32), (2048, 32)]
+GN_S = [1, 2, 31, 32, 33, 127, 128, 129, 257]
+GN_FRAMES = [1, 3]
+
+
+def gn_case(Fr, S, C, seed=0):
+    """Random frames; with three frames the middle one carries a +40 offset (the old test's stress)."""
+    x = gn_input(Fr, S, C, seed=seed + S + C)
+    if Fr == 3:
+        x[1] += 40.0
+        x = x.half().float()
+    return x
+
+
+# (S, C, v0): the sizes at which an outlier at the group's first position broke the first-value shift
+GN_OUTLIER_SIZES = [(5476, 256, 1000.0), (1369, 1024, 2000.0), (21904, 256, 60000.0)]
+GN_OUTLIER_KINDS = ("first", "first_sigma0.01", "middle", "first_frame1of3")
+
+
+def gn_outlier_case(S, C, v0, kind, groups=32):
+    """One massive activation v0 per frame in groups 0 and 5: at the group's first value of the frame (row 0, the
+    group's first channel), or in the middle of the map; the rest N(0.3, sigma).  Returns (x [F, S, C], frame that
+    carries the outlier).  |z| <= sqrt(S cg) ~ 420 at most, finite in fp16."""
+    Fr, fo = (3, 1) if kind == "first_frame1of3" else (1, 0)
+    x = gn_input(Fr, S, C, seed=S + C, sigma=0.01 if "sigma" in kind else 1.0)
+    cg = C // groups
+    row = S // 2 + 3 if kind == "middle" else 0
+    off = cg // 2 if kind == "middle" else 0
+    for grp in (0, 5):
+        x[fo, row, grp * cg + off] = v0
+    return x, fo
+
+
+# (C, S, F): M = F S in {1, 15, 16, 17, 128 k +- 1}; S = 5: a 16-row tile spans up to four frames; the last one has
+# more 16-row tiles than 8 waves x 256 CUs, so both register sets of the tile loop run
+GNL_CASES = [(64, 1, 1), (128, 15, 1), (256, 16, 1), (64, 17, 1), (128, 7, 55), (256, 7, 73), (64, 37, 83), (128, 15, 17),
+             (256, 17, 15), (64, 5, 7), (256, 5, 7), (128, 16, 3), (64, 37, 900)]
+
+
+# =====================================================================================================
+# Bilinear resize (csrc/vda_misc.hip upsample_kernel), NHWC
+# =====================================================================================================
+def _resize_err(x, Ho, Wo):
+    """x [BT, H, W, C] float64 -> (ref, A, epos) NHWC: the float64 resize, the resize of |x| and the value error of
+    the kernel's fp32 coordinates.  ac_coord / the kernel's x loop (vda_misc.hip:37-43, :81-83): sc = fl((in - 1) /
+    (out - 1)), i0 = (int)fl(sc * o), w = fma(sc, o, -i0): the blend is evaluated at p~ = i0 + w with |p~ - p| <=
+    u32 (p + |w|) <= u32 in.  When p is an integer, (int) may fall one cell short (w ~ 1) or land on it (w ~ 0):
+    bilinear interpolation is continuous across cells, so either way the value moves by at most |p~ - p| times the
+    largest difference of horizontally (vertically) adjacent source values of that frame and channel."""
+    BT, H, W, C = x.shape
+    xc = x.permute(0, 3, 1, 2)
+    ref, A = bilinear64(xc, Ho, Wo).permute(0, 2, 3, 1), bilinear64(xc.abs(), Ho, Wo).permute(0, 2, 3, 1)
+    z = torch.zeros(BT, 1, 1, C, dtype=torch.float64)
+    Dx = (x[:, :, 1:] - x[:, :, :-1]).abs().amax((1, 2), keepdim=True) if W > 1 else z
+    Dy = (x[:, 1:] - x[:, :-1]).abs().amax((1, 2), keepdim=True) if H > 1 else z
+    return ref, A, U32 * (W * Dx + H * Dy)
+
+
+def upsample_ref_bound(x, Ho, Wo):
+    """vda_upsample_bilinear on x [BT, H, W, C] (fp16 values) -> (ref, bound) [BT, Ho, Wo, C]: bilinear64 as the
+    reference; bilerp8 (vda_common.h:68-78) forms ux = 1 - wx, top = fma(wx, b, ux * a), bot likewise, o =
+    fp16(fma(wy, bot, (1 - wy) * top)): six fp32 roundings, each relative to a partial blend of |corners| (<= the
+    resize A of |x|), 8 u32 A with the second-order terms; the coordinates' error _resize_err; one fp16 rounding."""
+    ref, A, epos = _resize_err(d(x), Ho, Wo)
+    return ref, U16 * ref.abs() + 8 * U32 * A + epos + SUB16
+
+
+def emulate_upsample(x, Ho, Wo, stale_pair=False):
+    """The kernel's fp32 arithmetic per output.  stale_pair: a MUTANT whose second row of every row pair blends the
+    FIRST row's two source rows (with its own wy) even when it may not share them (test_fp16_bounds.py only)."""
+    x = x.detach().to("cpu", torch.float32)
+    BT, H, W, C = x.shape
+
+    def coord(n_in, n_out):
+        o = torch.arange(n_out, dtype=torch.float32)
+        sc = torch.tensor(float(n_in - 1), dtype=torch.float32) / torch.tensor(float(n_out - 1), dtype=torch.float32) \
+            if n_out > 1 else torch.zeros((), dtype=torch.float32)
+        i0 = (sc * o).to(torch.int64)
+        return i0, (i0 + 1).clamp_max(n_in - 1), fma32(sc.expand_as(o), o, -i0.float())
+    y0, y1, wy = coord(H, Ho)
+    x0, x1, wx = coord(W, Wo)
+    r = torch.arange(BT * Ho)
+    bt, oy = r // Ho, r % Ho
+    ya, yb, wyr = y0[oy], y1[oy], wy[oy]
+    if stale_pair:
+        first = r - (r % 2)
+        ya, yb, bt = ya[first], yb[first], bt[first]
+    wxv, wyv = wx.view(1, Wo, 1), wyr.view(-1, 1, 1)
+    ux, uy = 1.0 - wxv, 1.0 - wyv
+    xf = x.reshape(BT * H, W, C)
+    ra, rb = xf[bt * H + ya], xf[bt * H + yb]  # [rows, W, C]
+    e = lambda t: t.expand(BT * Ho, Wo, C)  # noqa: E731
+    top = fma32(e(wxv), ra[:, x1], e(ux) * ra[:, x0])
+    bot = fma32(e(wxv), rb[:, x1], e(ux) * rb[:, x0])
+    return fma32(e(wyv), bot, e(uy) * top).half().view(BT, Ho, Wo, C)
+
+
+# (BT, H, W, C, Ho, Wo)
+UPSAMPLE_CASES = [
+    (2, 1, 1, 8, 5, 7), (2, 5, 7, 8, 1, 1), (1, 5, 7, 32, 1, 9), (2, 9, 11, 40, 9, 11),    # from 1x1, to 1x1, 1 x Wo, identity
+    (2, 19, 19, 32, 38, 38), (2, 19, 19, 32, 37, 37),                                      # x2 exactly, x2 - 1
+    (2, 37, 37, 8, 19, 19), (1, 37, 37, 32, 5, 5),                                         # downscales: pairs never share
+    (2, 4, 5, 8, 9, 11), (3, 4, 5, 40, 9, 6), (3, 3, 3, 8, 7, 5),                          # Ho odd: a pair straddles frames; BT Ho odd
+    (2, 6, 1, 8, 13, 1), (1, 3, 1, 32, 7, 5),                                              # W = 1
+    (1, 5, 8, 256, 9, 15), (1, 5, 8, 256, 9, 16), (1, 5, 8, 256, 9, 17), (1, 5, 8, 256, 9, 33),  # Wo C / 8 = 480, 512, 544, 1056
+    (5, 2, 1, 8, 26215, 2),                                                                # 131,075 rows: the gridDim.y stride loop
+]
+
+
+def upsample_input(BT, H, W, C, kind="rand", seed=0):
+    if kind == "rand":
+        return rnd16(BT, H, W, C, seed=seed + H + W + C)
+    i = torch.arange(H).view(1, H, 1, 1) + torch.arange(W).view(1, 1, W, 1) + torch.arange(C).view(1, 1, 1, C)
+    return ((i % 2) * 2.0 - 1.0).expand(BT, H, W, C).contiguous() * 60000.0  # checkerboard: corner differences 120,000
+
+
+# =====================================================================================================
+# im2col (exact): index gathers
+# =====================================================================================================
+def patch_im2col_ref(img, Kp):
+    """A [BT (1 + np), Kp] fp16 of img [BT, 3, H, W] fp32: row 0 of each frame zero, then the 14 x 14 patches in
+    row-major order with k = ci * 196 + ky * 14 + kx, zero beyond 588; the one rounding is fp16(float)."""
+    BT, _, H, W = img.shape
+    ph, pw = H // 14, W // 14
+    p = img.cpu().view(BT, 3, ph, 14, pw, 14).permute(0, 2, 4, 1, 3, 5).reshape(BT, ph * pw, 588)
+    a = torch.zeros(BT, 1 + ph * pw, Kp)
+    a[:, 1:, :588] = p
+    return a.half().view(-1, Kp)
+
+
+def conv_im2col_ref(x, ks, stride, pad):
+    """A [BT Ho Wo, ks ks Cin] of NHWC x: k = (ky, kx, ci), zeros outside the image."""
+    BT, H, W, C = x.shape
+    Ho, Wo = (H + 2 * pad - ks) // stride + 1, (W + 2 * pad - ks) // stride + 1
+    xp = F.pad(x, (0, 0, pad, pad, pad, pad))
+    oy, ox = torch.arange(Ho) * stride, torch.arange(Wo) * stride
+    taps = [xp[:, oy + ky][:, :, ox + kx] for ky in range(ks) for kx in range(ks)]
+    return torch.stack(taps, 3).reshape(BT * Ho * Wo, ks * ks * C)
+
+
+# =====================================================================================================
+# Depth tail (csrc/vda_depth_head.hip -> vda_dconv.hip / vda_depth.hip / the implicit-GEMM depth kernel)
+# =====================================================================================================
+def split_hi_lo(w1):
+    """The fp32 3x3 weights [32, C, 3, 3] as the fp16 pair the kernels multiply: hi = fp16(w), lo = fp16(w - hi)."""
+    hi = w1.half()
+    return hi, (w1 - hi.float()).half()
+
+
+def depth_head_ref_bound(x, w1, b1, w2, b2, Ho, Wo):
+    """depth = relu(b2 + sum_j w2[j] relu(b1[j] + conv3x3_j(U))), U = fp16(resize(x)), x [BT, C, H, W] (fp16
+    values), w1 [32, C, 3, 3] fp32, w2 [32] -> (ref, bound) [BT, Ho, Wo], fp32 output (no fp16 store).
+
+    Reference: float64 resize, rounded to fp16, then the conv with the weights hi + lo the kernels really
+    multiply (split_hi_lo), everything else float64.  Kernel (vda_dconv.hip:1-11, :392-396; the halo kernels of
+    vda_depth.hip and the implicit-GEMM depth tail keep the same terms): 64 MFMA rows, hi and lo accumulated
+    separately in fp32 over K = 9 C products each, h_j = relu(acc_hi + acc_lo + b1): gamma(K + 3) of the absolute
+    image; then 4 products per lane, two lane-group shuffles and b2: gamma(32 + 2) of sum |w2 h| + |b2|.
+    The resized map: the kernels blend in fp32 (bilerp8, _resize_err) and round to fp16, so an element whose
+    float64 value lies within that fp32 error e32 of an fp16 rounding boundary may round the other way, a whole
+    fp16 ulp; only those elements are budgeted (dU = ulp where the distance to the boundary is <= e32, else 0),
+    carried through |hi + lo| as conv_ref_bound(up=...) carries its dx."""
+    x, w1, b1, w2, b2 = map(d, (x, w1, b1, w2, b2))
+    hi, lo = split_hi_lo(w1.float())
+    hi, lo = hi.double(), lo.double()
+    xn = x.permute(0, 2, 3, 1)
+    u64, A, epos = _resize_err(xn, Ho, Wo)
+    e32 = 8 * U32 * A + epos
+    U = u64.half().double()
+    ulp = torch.where(u64.abs() >= 2.0 ** -14, 2.0 ** (torch.floor(torch.log2(u64.abs().clamp_min(2.0 ** -14))) - 10),
+                      torch.full_like(u64, 2.0 ** -24))
+    dU = torch.where(0.5 * ulp - (u64 - U).abs() <= e32, 2 * ulp, torch.zeros_like(ulp))  # 2 ulp: a binade edge
+    U, dU = U.permute(0, 3, 1, 2), dU.permute(0, 3, 1, 2)
+    K = 9 * x.shape[1]
+    pre = F.conv2d(U, hi + lo, b1, padding=1)
+    Ah = F.conv2d(U.abs(), hi.abs() + lo.abs(), b1.abs(), padding=1)
+    dh = gam(K + 3) * Ah + F.conv2d(dU, (hi + lo).abs(), None, padding=1)
+    hj = pre.clamp_min(0)
+    w2v = w2.view(1, -1, 1, 1)
+    out = (hj * w2v).sum(1) + b2
+    dout = (dh * w2v.abs()).sum(1) * (1 + gam(34)) + gam(32 + 2) * ((hj * w2v).abs().sum(1) + b2.abs())
+    return out.clamp_min(0), dout + 2.0 ** -60
+
+
+def emulate_depth_head(x, w1, b1, w2, b2, Ho, Wo, no_relu=False):
+    """fp32: the emulated resize rounded to fp16, the hi and lo convs accumulated separately, the fp32 tail.
+    no_relu: a MUTANT without the ReLU between the 3x3 and the 1x1 conv (test_fp16_bounds.py only)."""
+    x, w1, b1, w2, b2 = (t.detach().to("cpu", torch.float32) for t in (x, w1, b1, w2, b2))
+    U = emulate_upsample(x.permute(0, 2, 3, 1), Ho, Wo).float().permute(0, 3, 1, 2)
+    hi, lo = split_hi_lo(w1)
+    hj = F.conv2d(U, hi.float(), None, padding=1) + F.conv2d(U, lo.float(), None, padding=1) + b1.view(1, -1, 1, 1)
+    if not no_relu:
+        hj = F.relu(hj)
+    return F.relu((hj * w2.view(1, -1, 1, 1)).sum(1) + b2)
+
+
+def depth_head_case(C, Hin, Win, BT, seed=0):
+    x = rnd16(BT, C, Hin, Win, seed=seed + 45)
+    w1 = torch.randn(32, C, 3, 3, generator=torch.Generator().manual_seed(seed + 46)) * (9 * C) ** -0.5
+    return x, w1, rnd32(32, scale=0.1, seed=seed + 47), rnd32(32, seed=seed + 48).abs() * 0.2, torch.tensor([0.05])
+
+
+# (C, Hin, Win, Ho, Wo): C = 40 takes the implicit-GEMM depth kernel (C % 32 != 0); 37 -> 19 is the downscale
+DEPTH_CASES = [(32, 1, 1, 1, 1), (64, 1, 1, 16, 16), (128, 9, 9, 15, 17), (64, 8, 20, 33, 47), (32, 16, 16, 16, 16),
+               (64, 37, 37, 19, 19), (40, 9, 9, 15, 17)]

@@ -208,102 +208,144 @@ __global__ __launch_bounds__(256) void groupnorm_kernel(const h16* __restrict__ 
 }
 
 // GroupNorm, three coalesced passes over [F, S, C] (used when the caller passes a workspace):
-//   gn_partial:  block (frame, chunk of gn_rows(C) rows) reads whole rows (16 B per thread) and writes
-//                per-channel partial sums of d and d^2, d = x - shift_g (shift_g = the group's first
-//                value of the frame, so the one-pass variance does not cancel);
-//   gn_finalize: per (frame, group) mean and rstd from the partials, fixed summation order;
+//   gn_partial:  block (frame, chunk of gn_rows(C) rows) reads whole rows (16 B per thread) ONCE into
+//                registers and writes, per channel, the chunk's mean and its centred second moment
+//                M2 = sum (x - chunk mean)^2: two passes over the registers, the mean going through LDS;
+//   gn_finalize: per (frame, group) mean and rstd by the parallel-variance merge of the (chunk, channel)
+//                pairs, mean = sum n_i mean_i / n, M2 = sum M2_i + n_i (mean_i - mean)^2, fixed
+//                summation order;
 //   gn_apply:    y = (x - mean) * rstd * gamma + beta, same row-chunk grid.
+// Every second moment is taken about the mean of the very values it sums and every merge term is
+// >= 0: no difference of two large sums anywhere, so no value, wherever it lies and however large it
+// is, makes the variance cancel.  (Before this form gn_partial summed d and d^2 with d = x - the group's
+// first value of the frame and gn_finalize formed a2 / n - md^2: exact for a common offset, but an
+// outlier AT that first position made md^2 ~ a2 / n ~ v0^2 and the variance their small difference:
+// rstd off by 1e-3 .. 1e-1, and 1 / sqrt(eps) once the difference went negative.  A variant that takes
+// the second moment about each thread's own mean and merges the row-lanes in LDS behind one barrier
+// measured 1.5 - 2.7 us slower per call than this one: the serial merge costs more than two barriers.)
 // Deterministic (no atomics).  The per-(frame, group) kernel above reads strided 16-B slivers of
 // every row three times; these read each row once per pass with full-row coalescing.
 // Rows per (frame, chunk) block: 128, or 32 for C >= 512 (there 128 rows are 64 sequential loads per
 // thread and a 19^2 map gave 96 blocks for 256 CUs: 34.7 us for 24 MB, round 4's forward trace)
 __host__ __device__ constexpr int gn_rows(int C) { return C >= 512 ? 32 : 128; }
 
-__device__ __forceinline__ void gn_layout(int C, int& cpr, int& rpi) {
+__host__ __device__ __forceinline__ void gn_layout(int C, int& cpr, int& rpi) {
   cpr = C >> 3;          // 8-channel chunks per row
   rpi = 256 / cpr;       // rows per block iteration
 }
 
-__device__ __forceinline__ void gn_partial_block(const h16* __restrict__ x, float* __restrict__ part, int S, int C,
-                                                 int groups, int nchunk, int bid, float* red) {
-  const int f = bid / nchunk, ch = bid % nchunk;
+// NR >= ceil(gn_rows(C) / rpi): the rows one thread holds (16 B each) between the two passes
+template <int NR>
+__global__ __launch_bounds__(256) void gn_partial_kernel(const h16* __restrict__ x, float* __restrict__ part, int S, int C,
+                                                         int nchunk) {
+  __shared__ float red[256 * 8];  // [thread][8 channels] partial sums (8 KB), used by both passes
+  __shared__ float cmean[2048];   // the chunk's per-channel mean (C <= 2048)
+  const int f = blockIdx.x / nchunk, ch = blockIdx.x % nchunk;
   int cpr, rpi;
   gn_layout(C, cpr, rpi);
   const int tid = threadIdx.x;
   const int cc = tid % cpr, r0 = tid / cpr;
-  const int cg = C / groups;
   const h16* fx = x + (long)f * S * C;
-  float sh[8], s1[8], s2[8];
+  const int rbeg = ch * gn_rows(C), rend = min(S, rbeg + gn_rows(C));
+  const int last = r0 < rpi ? rend : 0;  // the idle threads of a ragged layout (256 % cpr != 0) own no row
+  uint4 buf[NR];
+#pragma unroll
+  for (int i = 0; i < NR; ++i) {
+    const int r = rbeg + r0 + i * rpi;
+    buf[i] = r < last ? ldg16(fx + (long)r * C + cc * 8) : make_uint4(0u, 0u, 0u, 0u);
+  }
+  float s[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) s[j] = 0.f;
+#pragma unroll
+  for (int i = 0; i < NR; ++i) {  // absent rows are zeros
+    const h8 v = __builtin_bit_cast(h8, buf[i]);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) s[j] += (float)v[j];
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) red[tid * 8 + j] = s[j];
+  __syncthreads();
+  float m[8];
+  if (tid < cpr) {  // fold the rpi row-lanes of chunk column tid, fixed order
+#pragma unroll
+    for (int j = 0; j < 8; ++j) m[j] = 0.f;
+    for (int q = 0; q < rpi; ++q) {
+      const float* rr = &red[(q * cpr + tid) * 8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) m[j] += rr[j];
+    }
+    const float inv = 1.f / (float)(rend - rbeg);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      m[j] *= inv;
+      cmean[tid * 8 + j] = m[j];
+    }
+  }
+  __syncthreads();  // cmean written; every read of red's first use is done
+  float cm[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
-    sh[j] = (float)fx[((cc * 8 + j) / cg) * cg];
-    s1[j] = 0.f;
-    s2[j] = 0.f;
+    cm[j] = cmean[cc * 8 + j];
+    s[j] = 0.f;
   }
-  if (r0 < rpi) {
-    const int rend = min(S, (ch + 1) * gn_rows(C));
-#pragma unroll 4
-    for (int r = ch * gn_rows(C) + r0; r < rend; r += rpi) {
-      const h8 v = __builtin_bit_cast(h8, ldg16(fx + (long)r * C + cc * 8));
+#pragma unroll
+  for (int i = 0; i < NR; ++i) {
+    if (rbeg + r0 + i * rpi < last) {
+      const h8 v = __builtin_bit_cast(h8, buf[i]);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        const float d = (float)v[j] - sh[j];
-        s1[j] += d;
-        s2[j] = fmaf(d, d, s2[j]);
+        const float d = (float)v[j] - cm[j];
+        s[j] = fmaf(d, d, s[j]);
       }
     }
   }
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    red[tid * 16 + j] = s1[j];
-    red[tid * 16 + 8 + j] = s2[j];
-  }
+  for (int j = 0; j < 8; ++j) red[tid * 8 + j] = s[j];
   __syncthreads();
-  if (tid < cpr) {  // fold the rpi row-lanes of chunk column tid, fixed order
-    float a1[8], a2[8];
+  if (tid < cpr) {
+    float a2[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { a1[j] = 0.f; a2[j] = 0.f; }
+    for (int j = 0; j < 8; ++j) a2[j] = 0.f;
     for (int q = 0; q < rpi; ++q) {
-      const float* rr = &red[(q * cpr + tid) * 16];
+      const float* rr = &red[(q * cpr + tid) * 8];
 #pragma unroll
-      for (int j = 0; j < 8; ++j) { a1[j] += rr[j]; a2[j] += rr[8 + j]; }
+      for (int j = 0; j < 8; ++j) a2[j] += rr[j];
     }
     float* out = part + ((long)(f * nchunk + ch) * C + tid * 8) * 2;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { out[2 * j] = a1[j]; out[2 * j + 1] = a2[j]; }
+    for (int j = 0; j < 8; ++j) { out[2 * j] = m[j]; out[2 * j + 1] = a2[j]; }
   }
 }
 
-__global__ __launch_bounds__(256) void gn_partial_kernel(const h16* __restrict__ x, float* __restrict__ part, int S, int C,
-                                                         int groups, int nchunk) {
-  __shared__ float red[256 * 16];  // [thread][sum d x8 | sum d^2 x8] (16 KB)
-  gn_partial_block(x, part, S, C, groups, nchunk, blockIdx.x, red);
-}
-
-
-__global__ __launch_bounds__(64) void gn_finalize_kernel(const h16* __restrict__ x, const float* __restrict__ part,
-                                                         float* __restrict__ stats, int S, int C, int groups, int nchunk,
-                                                         float eps) {
+__global__ __launch_bounds__(64) void gn_finalize_kernel(const float* __restrict__ part, float* __restrict__ stats, int S,
+                                                         int C, int groups, int nchunk, float eps) {
   const int f = blockIdx.x / groups, g = blockIdx.x % groups;
   const int cg = C / groups;
   const int lane = threadIdx.x;
-  float a1 = 0.f, a2 = 0.f;
   const int n = nchunk * cg;
+  const float cnt = (float)S * (float)cg;
+  float a1 = 0.f;
 #pragma unroll 8  // loads in flight; the sums keep their order
   for (int i = lane; i < n; i += 64) {
     const int chn = i / cg, c = g * cg + (i - chn * cg);
-    const float* p = part + ((long)(f * nchunk + chn) * C + c) * 2;
-    a1 += p[0];
-    a2 += p[1];
+    const float rows = (float)min(gn_rows(C), S - chn * gn_rows(C));
+    a1 = fmaf(rows, part[((long)(f * nchunk + chn) * C + c) * 2], a1);
   }
-  a1 = wave_sum(a1);
+  const float mean = wave_sum(a1) / cnt;
+  float a2 = 0.f;
+#pragma unroll 8
+  for (int i = lane; i < n; i += 64) {
+    const int chn = i / cg, c = g * cg + (i - chn * cg);
+    const float rows = (float)min(gn_rows(C), S - chn * gn_rows(C));
+    const float* p = part + ((long)(f * nchunk + chn) * C + c) * 2;
+    const float d = p[0] - mean;
+    a2 += fmaf(rows * d, d, p[1]);
+  }
   a2 = wave_sum(a2);
   if (lane == 0) {
-    const float cnt = (float)S * (float)cg;
-    const float md = a1 / cnt;
-    const float var = fmaxf(a2 / cnt - md * md, 0.f);
-    stats[(f * groups + g) * 2] = (float)x[(long)f * S * C + g * cg] + md;
-    stats[(f * groups + g) * 2 + 1] = rsqrtf(var + eps);
+    stats[(f * groups + g) * 2] = mean;
+    stats[(f * groups + g) * 2 + 1] = rsqrtf(a2 / cnt + eps);
   }
 }
 
@@ -537,6 +579,25 @@ extern "C" int vda_layernorm(const void* x, int64_t ldx, void* y, const float* g
   return 0;
 }
 
+// gn_partial + gn_finalize: part = ws [F, nchunk, C, 2] (chunk mean, chunk M2), stats [F, groups, 2] (mean, rstd)
+static void gn_stats_launch(const h16* x, float* part, float* stats, int F, int S, int C, int groups, int nchunk,
+                            float eps, hipStream_t st) {
+  int cpr, rpi;
+  gn_layout(C, cpr, rpi);
+  const int nr = (gn_rows(C) + rpi - 1) / rpi;  // rows per thread: <= 32 (cpr <= 63 at 128 rows, rpi >= 1 at 32)
+  const dim3 grid(F * nchunk), blk(256);
+  if (nr <= 4)
+    hipLaunchKernelGGL(gn_partial_kernel<4>, grid, blk, 0, st, x, part, S, C, nchunk);
+  else if (nr <= 8)
+    hipLaunchKernelGGL(gn_partial_kernel<8>, grid, blk, 0, st, x, part, S, C, nchunk);
+  else if (nr <= 16)
+    hipLaunchKernelGGL(gn_partial_kernel<16>, grid, blk, 0, st, x, part, S, C, nchunk);
+  else
+    hipLaunchKernelGGL(gn_partial_kernel<32>, grid, blk, 0, st, x, part, S, C, nchunk);
+  hipLaunchKernelGGL(gn_finalize_kernel, dim3(F * groups), dim3(64), 0, st, (const float*)part, stats, S, C, groups, nchunk,
+                     eps);
+}
+
 extern "C" int64_t vda_groupnorm_workspace(int32_t F, int32_t S, int32_t C, int32_t groups) {
   if (F <= 0 || S <= 0 || C <= 0 || groups <= 0) return 0;
   const long nchunk = (S + gn_rows(C) - 1) / gn_rows(C);
@@ -553,9 +614,7 @@ extern "C" int vda_groupnorm(const void* x, void* y, const float* gamma, const f
   if (ws && C % 8 == 0 && C <= 2048) {
     const int nchunk = (S + gn_rows(C) - 1) / gn_rows(C);
     float* stats = ws + 2L * F * nchunk * C;
-    hipLaunchKernelGGL(gn_partial_kernel, dim3(F * nchunk), dim3(256), 0, st, (const h16*)x, ws, S, C, groups, nchunk);
-    hipLaunchKernelGGL(gn_finalize_kernel, dim3(F * groups), dim3(64), 0, st, (const h16*)x, (const float*)ws, stats, S,
-                       C, groups, nchunk, eps);
+    gn_stats_launch((const h16*)x, ws, stats, F, S, C, groups, nchunk, eps, st);
     hipLaunchKernelGGL(gn_apply_kernel, dim3(F * nchunk), dim3(256), 0, st, (const h16*)x, (h16*)y, (const float*)stats,
                        gamma, beta, S, C, groups, nchunk);
     VDA_LAUNCH_CHECK();
@@ -618,9 +677,7 @@ extern "C" int vda_groupnorm_linear(const void* x, const float* gamma, const flo
   float* stats = wsf + 2L * F * nchunk * C;
   const int ntiles = (M + 15) / 16;
   const int nblk = std::min(vda_cu_count(), (ntiles + GNL_WAVES - 1) / GNL_WAVES);
-  hipLaunchKernelGGL(gn_partial_kernel, dim3(F * nchunk), dim3(256), 0, st, (const h16*)x, wsf, S, C, groups, nchunk);
-  hipLaunchKernelGGL(gn_finalize_kernel, dim3(F * groups), dim3(64), 0, st, (const h16*)x, (const float*)wsf, stats, S,
-                     C, groups, nchunk, eps);
+  gn_stats_launch((const h16*)x, wsf, stats, F, S, C, groups, nchunk, eps, st);
 #define VDA_GNL(KK)                                                                                                 \
   hipLaunchKernelGGL(gn_linear_kernel<KK>, dim3(nblk), dim3(64 * GNL_WAVES), 0, st, (const h16*)x, (const float*)stats, \
                      (const h16*)w, gamma, beta, bias, (h16*)y, stats_out, M, S, ntiles)
