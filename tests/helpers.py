@@ -42,6 +42,20 @@ def rel_l1(a, b):
     return vda_oracle.rel_l1(a, b)
 
 
+def device_at_offset(a: np.ndarray, offset: int = 1, fill=None) -> torch.Tensor:
+    """a on the GPU with its shape, starting ``offset`` elements past an allocation boundary (a multiple of 16
+    bytes): one fp32 element past it is 4-byte aligned, not 16.  ``fill``: the value of the buffer's elements
+    around a (unset otherwise)."""
+    flat = torch.from_numpy(np.array(a).reshape(-1))  # a copy: shared references may be read-only
+    buf = torch.empty(offset + flat.numel() + 16, dtype=flat.dtype, device="cuda")
+    if fill is not None:
+        buf.fill_(fill)
+    v = buf[offset:offset + flat.numel()]
+    v.copy_(flat)
+    assert v.data_ptr() % 16 == offset * flat.element_size() % 16
+    return v.view(a.shape)
+
+
 def assert_elementwise(y, ref64, bound64, what):
     """Assert |y - ref| <= bound at EVERY element (y any dtype / device; ref64, bound64 float64 of y's
     shape, a bound from tests/fp16_bounds.py).  A non-finite y counts as a violation.  The failure message

@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import GOLDEN, recipe_state_dict
+from helpers import GOLDEN, device_at_offset as offset_by_one, recipe_state_dict
 from vda_amd import _lib
 from vda_amd import video as V
 
@@ -23,13 +23,6 @@ pytestmark = pytest.mark.gpu
 def rel(a, b):
     a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
     return float(np.abs(a - b).sum() / np.abs(b).sum())
-
-
-def offset_by_one(a: np.ndarray) -> torch.Tensor:
-    """a on the GPU, starting one element past an allocation boundary (4-byte aligned, not 16)."""
-    buf = torch.empty(a.size + 8, dtype=torch.from_numpy(a[:1]).dtype, device="cuda")
-    buf[1:1 + a.size].copy_(torch.from_numpy(a))
-    return buf[1:1 + a.size]
 
 
 def closed_form(sums):
@@ -88,6 +81,29 @@ def test_scale_shift_kernel(n, masked):
     assert torch.equal(rss[:2].view(torch.int32), ss.cpu().view(torch.int32))
     assert torch.equal(rsums[:5].view(torch.int64), sums.cpu().view(torch.int64))
     assert torch.isnan(rss[2:]).all() and torch.isnan(rsums[5:]).all()
+
+
+@pytest.mark.parametrize("masked", [False, True])
+@pytest.mark.parametrize("off", [0, 1, 2, 3])
+def test_scale_shift_every_head_and_tail(off, masked):
+    """pred starts ``off`` elements past a 16-byte boundary (heads of 0, 3, 2, 1 elements), with runs shorter
+    than a head, shorter than one 16-byte group, and with every tail length."""
+    from vda_amd import ops
+    for n in (1, 2, 3, 4, 5, 7, 8, 1030):
+        g = np.random.default_rng(100 * n + 2 * off + masked)
+        p = (g.random(n) * 10 + 1).astype(np.float32)
+        t = (p * 1.3 - 0.7 + g.standard_normal(n) * 0.05).astype(np.float32)
+        m = g.integers(0, 2, n).astype(np.uint8) if masked else None
+        dp, dt = offset_by_one(p, off), offset_by_one(t, off)
+        dm = offset_by_one(m, off) if masked else None
+        assert dp.data_ptr() % 16 == 4 * off
+        _, sums = ops.scale_shift(dp, dt, mask=dm)
+        P, T = p.astype(np.float64), t.astype(np.float64)
+        M = np.ones(n) if m is None else m.astype(np.float64)
+        ref = np.array([np.sum(M * P * P), np.sum(M * P), np.sum(M), np.sum(M * P * T), np.sum(M * T)])
+        got = sums.cpu().numpy()
+        np.testing.assert_allclose(got, ref, rtol=1e-12, atol=0, err_msg=f"n {n}")
+        assert got[2] == ref[2], (n, got[2], ref[2])  # the count: exact
 
 
 def test_scale_shift_degenerate_systems_return_identity():

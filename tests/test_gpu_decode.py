@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import device_at_offset
 import vda_amd
 from vda_amd import _lib
 from vda_amd import decode as D
@@ -48,11 +49,7 @@ def on_device(pay, padded=False, offset=0):
     stride = (fsz + 15) // 16 * 16 if padded else fsz
     host = np.full((n, stride), 0xAA, np.uint8)
     host[:, :fsz] = pay
-    buf = torch.full((offset + n * stride + 16,), 0x55, dtype=torch.uint8, device="cuda")
-    v = buf[offset:offset + n * stride].view(n, stride)
-    v.copy_(torch.from_numpy(host))
-    assert v.data_ptr() % 16 == offset % 16
-    return v
+    return device_at_offset(host, offset, fill=0x55)
 
 
 VARIANTS = [dict(), dict(padded=True), dict(offset=1)]

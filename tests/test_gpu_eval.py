@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import GOLDEN, recipe_state_dict
+from helpers import GOLDEN, device_at_offset as offset_by_one, recipe_state_dict
 from test_eval import check_against_reference
 from vda_amd import _lib
 from vda_amd import evaluate as E
@@ -25,14 +25,6 @@ pytestmark = pytest.mark.gpu
 
 SHAPES = [(1, 1), (1, 3), (3, 63), (2, 64), (3, 257), (1, 4099), (33, 48 * 64), (2, 270 * 480)]
 MAX_DEPTH = 80.0
-
-
-def offset_by_one(a: np.ndarray) -> torch.Tensor:
-    """a on the GPU with its shape, starting one element past an allocation boundary (for floats: 4-byte
-    aligned, not 16)."""
-    buf = torch.empty(a.size + 8, dtype=torch.from_numpy(a.reshape(-1)[:1]).dtype, device="cuda")
-    buf[1:1 + a.size].copy_(torch.from_numpy(a.reshape(-1)))
-    return buf[1:1 + a.size].view(a.shape)
 
 
 def scene(F, S, masked, seed=0):
@@ -159,6 +151,26 @@ def test_depth_eval_fit_kernel(F, S, masked):
         rss, rsums = raw_fit(dp, dg, dv, F, S, per_frame)
         assert same_bits(rss[:2 * G], want_ss.reshape(-1)) and same_bits(rsums[:5 * G], want_sums.reshape(-1))
         assert torch.isnan(rss[2 * G:]).all() and torch.isnan(rsums[5 * G:]).all()
+
+
+@pytest.mark.parametrize("masked", [True, False])
+@pytest.mark.parametrize("off", [0, 1, 2, 3])
+def test_depth_eval_fit_every_head_and_tail(off, masked):
+    """pred starts ``off`` elements past a 16-byte boundary and frame 1 another S elements on, with frames
+    shorter than a head, shorter than one 16-byte group, and with every tail length."""
+    from vda_amd import ops
+    F = 2
+    for S in (1, 2, 3, 4, 5, 7, 8, 1030):
+        pred, gt, valid = scene(F, S, masked, seed=off)
+        dp, dg = offset_by_one(pred, off), offset_by_one(gt, off)
+        dv = None if valid is None else offset_by_one(valid.astype(np.uint8), off)
+        assert dp.data_ptr() % 16 == 4 * off
+        _, psums = ops.depth_eval_fit(dp, dg, dv, per_frame=True)
+        hs = psums.cpu().numpy()
+        for f in range(F):
+            ref = fit_sums_ref(pred[f], gt[f], None if valid is None else valid[f])
+            np.testing.assert_allclose(hs[f], ref, rtol=1e-12, atol=0, err_msg=f"S {S} frame {f}")
+            assert hs[f, 2] == ref[2], (S, f, hs[f, 2], ref[2])  # the count: exact
 
 
 def torch_aligned(dp, ss, F):

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import device_at_offset
 import vda_amd  # noqa: F401
 from vda_amd import _lib
 from vda_amd import video_io as VIO
@@ -47,9 +48,7 @@ def as_tensor(a):
 def on_device(d, offset):
     if not offset:
         return as_tensor(d).cuda()
-    buf = torch.empty(d.size + 1, dtype=torch.float32, device="cuda")
-    buf[1:].copy_(as_tensor(d).reshape(-1))
-    v = buf[1:].view(d.shape)
+    v = device_at_offset(d, 1)
     assert v.data_ptr() % 16 == 4 and v.is_contiguous()
     return v
 
@@ -146,6 +145,52 @@ def test_nothing_written_outside_the_output(shape, layout):
         torch.cuda.synchronize()
         assert bool((buf[:lead] == 0xA5).all()) and bool((buf[lead + n:] == 0xA5).all())
         assert torch.equal(buf[lead:lead + n], want)
+
+
+EDGE_RUNS = (1, 2, 3, 4, 5, 7, 8, 1030)
+
+
+@pytest.mark.parametrize("off", [0, 1, 2, 3])
+def test_range_every_head_and_tail(off):
+    """depth starts ``off`` elements past a 16-byte boundary (heads of 0, 3, 2, 1 elements), with runs shorter
+    than a head, shorter than one 16-byte group, and with every tail length; each element in turn holds the
+    extremes, so one that is skipped shows."""
+    for n in EDGE_RUNS:
+        d = np.random.default_rng(10 * n + off).uniform(0.2, 7.5, n).astype(np.float32)
+        for k in sorted({0, 1, 2, 3, n - 4, n - 3, n - 2, n - 1} & set(range(n))):
+            for v in (np.float32(0.1), np.float32(9.5)):
+                e = d.copy()
+                e[k] = v
+                r = VIS.LibVis.range(device_at_offset(e, off)).cpu().numpy()
+                assert r[0] == e.min() and r[1] == e.max(), (n, k, v, r)
+
+
+@pytest.mark.parametrize("layout", ["index", "hwc"])
+@pytest.mark.parametrize("off", [0, 1, 2, 3])
+def test_colorize_every_head_and_tail(off, layout):
+    """Two frames of S pixels, depth ``off`` elements past a 16-byte boundary, the output at byte offsets 0..3
+    inside a buffer of canary bytes: the host path's bytes, and nothing around them."""
+    lib = _lib.lib()
+    code = VIS.LAYOUTS[layout]
+    lut = None if layout == "index" else table()
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    for S in EDGE_RUNS:
+        d = np.random.default_rng(10 * S + off).uniform(0.2, 7.5, (2, 1, S)).astype(np.float32)
+        want = as_tensor(VIO.colorize_depths(d, grayscale=True) if layout == "index" else VIO.colorize_depths(d))
+        t = device_at_offset(d, off)
+        rng = VIS.LibVis.range(t)
+        n = lib.vda_depth_colorize_bytes(2, 1, S, code)
+        assert n == want.numel()
+        for lead in (64, 61, 62, 63):
+            buf = torch.full((lead + n + 67,), 0xA5, dtype=torch.uint8, device="cuda")
+            assert (buf.data_ptr() + lead) % 4 == lead % 4
+            rc = lib.vda_depth_colorize(ctypes.c_void_p(t.data_ptr()), 2, 1, S, ctypes.c_void_p(rng.data_ptr()),
+                                        None if lut is None else ctypes.c_void_p(lut.data_ptr()), code,
+                                        ctypes.c_void_p(buf.data_ptr() + lead), stream)
+            assert rc == 0, lib.vda_last_error()
+            torch.cuda.synchronize()
+            assert bool((buf[:lead] == 0xA5).all()) and bool((buf[lead + n:] == 0xA5).all()), (S, lead)
+            assert torch.equal(buf[lead:lead + n].cpu(), want.reshape(-1)), (S, lead)
 
 
 def test_range_from_the_whole_clip():

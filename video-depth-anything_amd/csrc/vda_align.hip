@@ -3,22 +3,18 @@
 //
 // scale_shift: compute_scale_and_shift (utils/util.py:40-62) as video_depth.py:393-395 (long video)
 // and :312-314 (streaming) call it: five masked sums over pred / target and the 2x2 solve.  The
-// reference sums in fp32 in numpy's pairwise order; here every sum is fp64 in a fixed order
-// (per thread -> wave butterfly -> block in wave order -> per-block partials in the caller's
-// workspace -> one wave adds the partials in index order and solves), so the result is the same bits
-// on every run and no atomics are involved.  HBM-bound: 8 B (9 B with a mask) per element.
+// reference sums in fp32 in numpy's pairwise order; here every sum is fp64 in the fixed order of the
+// streaming pass (vda_stream.h: 16-byte loads on pred, element-aligned ones on target / mask), and one
+// wave adds the partials and solves, so the result is the same bits on every run and no atomics are
+// involved.  HBM-bound: 8 B (9 B with a mask) per element.
 //
 // depth_align: video_depth.py:371 / :299 (resize) + :400-413 / :315 (affine, clip) + get_interpolate_frames
 // (utils/util.py:65-73, blend) in one pass, one thread per output pixel: the resized, unaligned
 // window is never written to HBM.  4 B read (through L1/L2) + 4 B written per element, + 4 B with a blend.
-#include "vda_common.h"
+#include "vda_stream.h"
 #include "../../include/vda.h"
 
 namespace {
-
-constexpr int kBlock = 256;
-constexpr int kWaves = kBlock / 64;
-constexpr int64_t kElemsPerBlock = (int64_t)kBlock * 4;  // one 16-byte load per thread and iteration
 
 struct Sums {
   double v[5];  // a_00 = S m p^2, a_01 = S m p, a_11 = S m, b_0 = S m p t, b_1 = S m t
@@ -34,80 +30,44 @@ __device__ __forceinline__ void accumulate(Sums& s, float p, float t, float m) {
   s.v[4] = fma(dm, dt, s.v[4]);
 }
 
-int scale_shift_grid(int64_t n) {
-  const int64_t want = (n + kElemsPerBlock - 1) / kElemsPerBlock;
-  const int64_t cap = 4 * (int64_t)vda_cu_count();
-  return (int)(want < 1 ? 1 : (want > cap ? cap : want));
-}
+// One 16-byte group per thread and iteration, at most 4 blocks per CU.
+int scale_shift_grid(int64_t n) { return stream_grid(n, kStreamGroup, 4 * (int64_t)vda_cu_count()); }
 
-// Block b leaves its five sums in part[b * 5 .. b * 5 + 4].  head = elements before pred's first
-// 16-byte boundary, nvec = 16-byte groups after it; block 0 also takes the head and the tail.
+// Block b leaves its five sums in part[b * 5 .. b * 5 + 4]; the split is pred's.
 template <bool MASK>
-__global__ __launch_bounds__(kBlock) void scale_shift_partial_kernel(const float* __restrict__ pred,
-                                                                     const float* __restrict__ target,
-                                                                     const uint8_t* __restrict__ mask, int64_t n,
-                                                                     int head, int64_t nvec, double* __restrict__ part) {
+__global__ __launch_bounds__(kStreamBlock) void scale_shift_partial_kernel(const float* __restrict__ pred,
+                                                                           const float* __restrict__ target,
+                                                                           const uint8_t* __restrict__ mask, int64_t n,
+                                                                           double* __restrict__ part) {
   Sums s = {{0., 0., 0., 0., 0.}};
-  const float* pb = pred + head;
-  const float* tb = target + head;
-  const uint8_t* mb = MASK ? mask + head : nullptr;
-  const int64_t stride = (int64_t)gridDim.x * kBlock;
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < nvec; i += stride) {
-    const f4 p = *reinterpret_cast<const f4*>(pb + 4 * i);
-    const f4a4 t = *reinterpret_cast<const f4a4*>(tb + 4 * i);
-    float m[4] = {1.f, 1.f, 1.f, 1.f};
-    if (MASK) {
-      const u8x4a1 mv = *reinterpret_cast<const u8x4a1*>(mb + 4 * i);
+  const StreamSplit sp = stream_split_f32(pred, n);
+  stream_walk(
+      n, sp.head, sp.nvec,
+      [&](int64_t o) {
+        const f4 p = *reinterpret_cast<const f4*>(pred + o);
+        const f4a4 t = *reinterpret_cast<const f4a4*>(target + o);
+        float m[4] = {1.f, 1.f, 1.f, 1.f};
+        if (MASK) {
+          const u8x4a1 mv = *reinterpret_cast<const u8x4a1*>(mask + o);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) m[j] = (float)mv[j];
-    }
+          for (int j = 0; j < 4; ++j) m[j] = (float)mv[j];
+        }
 #pragma unroll
-    for (int j = 0; j < 4; ++j) accumulate(s, p[j], t[j], m[j]);
-  }
-  if (blockIdx.x == 0) {
-    const int64_t tail0 = head + 4 * nvec;
-    const int tail = (int)(n - tail0);  // 0..3
-    int64_t e = -1;
-    if ((int)threadIdx.x < head) e = threadIdx.x;
-    else if ((int)threadIdx.x >= 8 && (int)threadIdx.x - 8 < tail) e = tail0 + (threadIdx.x - 8);
-    if (e >= 0) accumulate(s, pred[e], target[e], MASK ? (float)mask[e] : 1.f);
-  }
-  __shared__ double red[kWaves][5];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int j = 0; j < 5; ++j) {
-    const double w = wave_sum_f64(s.v[j]);
-    if (lane == 0) red[wave][j] = w;
-  }
-  __syncthreads();
-  if (threadIdx.x < 5) {
-    double a = red[0][threadIdx.x];
-#pragma unroll
-    for (int w = 1; w < kWaves; ++w) a += red[w][threadIdx.x];
-    part[(int64_t)blockIdx.x * 5 + threadIdx.x] = a;
-  }
+        for (int j = 0; j < 4; ++j) accumulate(s, p[j], t[j], m[j]);
+      },
+      [&](int64_t e) { accumulate(s, pred[e], target[e], MASK ? (float)mask[e] : 1.f); });
+  block_store_partial<5>(s.v, part + (int64_t)blockIdx.x * 5);
 }
 
-// One wave: lane l adds partials l, l + 64, ... in index order, a butterfly adds the lanes, lane 0
-// solves the 2x2 system in fp64 (the plain closed form, no contraction) and rounds once on the store.
+// One wave adds the partials, lane 0 solves the 2x2 system (singular: the identity) and rounds once on
+// the store.
 __global__ __launch_bounds__(64) void scale_shift_solve_kernel(const double* __restrict__ part, int nparts,
                                                                double* __restrict__ sums, float* __restrict__ ss) {
-  double a[5] = {0., 0., 0., 0., 0.};
-  for (int b = threadIdx.x; b < nparts; b += 64) {
-#pragma unroll
-    for (int j = 0; j < 5; ++j) a[j] += part[(int64_t)b * 5 + j];
-  }
-#pragma unroll
-  for (int j = 0; j < 5; ++j) a[j] = wave_sum_f64(a[j]);
+  double a[5];
+  wave_add_partials<5>(part, nparts, 5, [&](int j, double v) { a[j] = v; });
   if (threadIdx.x == 0) {
-#pragma clang fp contract(off)
-    const double a00 = a[0], a01 = a[1], a11 = a[2], b0 = a[3], b1 = a[4];
-    const double det = a00 * a11 - a01 * a01;
     double x0 = 1., x1 = 0.;
-    if (det != 0.) {
-      x0 = (a11 * b0 - a01 * b1) / det;
-      x1 = (-a01 * b0 + a00 * b1) / det;
-    }
+    solve_2x2(a, x0, x1);
     if (sums) {
 #pragma unroll
       for (int j = 0; j < 5; ++j) sums[j] = a[j];
@@ -169,16 +129,13 @@ extern "C" int vda_scale_shift(const float* pred, const float* target, const uin
                 "pred / target / ss must be 4-byte aligned, sums and the workspace 8-byte aligned");
   VDA_CHECK_ARG(ws_bytes >= vda_scale_shift_workspace(n), "workspace smaller than vda_scale_shift_workspace(n)");
   const int grid = scale_shift_grid(n);
-  int64_t head = (int64_t)((16 - ((uintptr_t)pred & 15)) & 15) / 4;
-  if (head > n) head = n;
-  const int64_t nvec = (n - head) / 4;
   double* part = (double*)ws;
   if (mask)
-    hipLaunchKernelGGL(scale_shift_partial_kernel<true>, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, pred, target,
-                       mask, n, (int)head, nvec, part);
+    hipLaunchKernelGGL(scale_shift_partial_kernel<true>, dim3(grid), dim3(kStreamBlock), 0, (hipStream_t)stream, pred,
+                       target, mask, n, part);
   else
-    hipLaunchKernelGGL(scale_shift_partial_kernel<false>, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, pred, target,
-                       mask, n, (int)head, nvec, part);
+    hipLaunchKernelGGL(scale_shift_partial_kernel<false>, dim3(grid), dim3(kStreamBlock), 0, (hipStream_t)stream, pred,
+                       target, mask, n, part);
   VDA_LAUNCH_CHECK();
   hipLaunchKernelGGL(scale_shift_solve_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double*)part, grid, sums,
                      ss);

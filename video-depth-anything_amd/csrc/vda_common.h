@@ -18,8 +18,8 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef float f16x __attribute__((ext_vector_type(16)));
 // 16-byte groups of floats / 4-byte groups of mask bytes whose address is only element-aligned: in the
-// streaming reductions (vda_align.hip, vda_eval.hip) the other operands share pred's head, so their
-// body loads start wherever that leaves them
+// streaming passes (vda_stream.h) the other operands share the head of the one that sets the split, so
+// their body loads start wherever that leaves them
 typedef float f4a4 __attribute__((ext_vector_type(4), aligned(4)));
 typedef uint8_t u8x4a1 __attribute__((ext_vector_type(4), aligned(1)));
 

@@ -9,9 +9,8 @@
 //          SignedRelative, AbsoluteDifference, AbsoluteRelative, MeanSquared), ten full-size numpy passes
 //          in the reference, in one pass: eight fp64 sums per frame.
 //
-// Both follow vda_scale_shift (vda_align.hip): grid-stride with 16-byte loads on pred and element-aligned
-// vector loads on gt / valid, per thread -> wave butterfly -> block in wave order -> per-block partials in
-// the caller's workspace -> a small kernel adds a frame's partials in index order -> frames are added in
+// Both are streaming passes (vda_stream.h) per frame: 16-byte loads on pred and element-aligned vector
+// loads on gt / valid, a small kernel adds a frame's partials in index order, then the frames are added in
 // frame order.  No atomics, so the same input gives the same bits on every run.  Every frame has its own
 // head / tail (frames start at f * S, S is not a multiple of 4 in general) and its own blocks (grid.y = f),
 // and the number of blocks per frame depends on S alone: frame f of an [F, S] call is summed exactly as a
@@ -19,28 +18,22 @@
 // (no rcp, no contraction), so the aligned map equals separate torch fp32 ops bit for bit.  Invalid
 // pixels are selected out, never multiplied out: gt may be 0 or NaN there (1/0 = inf, inf * 0 = NaN).
 // HBM-bound: 9 B per element read (8 B without valid), + 4 B written with the aligned map.
-#include "vda_common.h"
+#include "vda_stream.h"
 #include "../../include/vda.h"
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kWaves = kBlock / 64;
 constexpr int kFitSums = 5;
 constexpr int kMetricSums = 8;
 constexpr int kPartStride = 8;  // doubles per block partial, for both kernels
 // A block takes at least kItersPerBlock 16-byte groups per thread while the frame is large enough;
 // at most kMaxBlocksPerFrame blocks share a frame.
-constexpr int64_t kElemsPerBlock = (int64_t)kBlock * 4;
 constexpr int64_t kItersPerBlock = 4;
 constexpr int64_t kMaxBlocksPerFrame = 512;
 constexpr int kMaxFrames = 65535;  // grid.y
 
 // Blocks per frame: a function of S alone (see the header comment).
-int blocks_per_frame(int64_t S) {
-  const int64_t want = (S + kElemsPerBlock * kItersPerBlock - 1) / (kElemsPerBlock * kItersPerBlock);
-  return (int)(want < 1 ? 1 : (want > kMaxBlocksPerFrame ? kMaxBlocksPerFrame : want));
-}
+int blocks_per_frame(int64_t S) { return stream_grid(S, kStreamGroup * kItersPerBlock, kMaxBlocksPerFrame); }
 
 // a_00 = S p^2, a_01 = S p, a_11 = S 1, b_0 = S p t, b_1 = S t over valid pixels, t = 1 / gt in fp32.
 // Branch-free: an invalid pixel's p and t are replaced by +0 before they reach a sum (a select, so a NaN
@@ -96,45 +89,24 @@ __device__ __forceinline__ void metric_accumulate(double (&s)[kMetricSums], int 
   s[7] += (double)sq;
 }
 
-template <int K>
-__device__ __forceinline__ void block_store_partial(const double (&s)[K], double* __restrict__ part) {
-  __shared__ double red[kWaves][K];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int j = 0; j < K; ++j) {
-    const double w = wave_sum_f64(s[j]);
-    if (lane == 0) red[wave][j] = w;
-  }
-  __syncthreads();
-  if (threadIdx.x < K) {
-    double a = red[0][threadIdx.x];
-#pragma unroll
-    for (int w = 1; w < kWaves; ++w) a += red[w][threadIdx.x];
-    part[threadIdx.x] = a;
-  }
-}
-
 // Frame f = blockIdx.y, block b = blockIdx.x of gridDim.x: the block's sums go to
-// part[(f * gridDim.x + b) * kPartStride ..].  head = elements before the first 16-byte boundary of the
-// frame's pred, nvec = 16-byte groups after it; block 0 of the frame also takes the head and the tail.
+// part[(f * gridDim.x + b) * kPartStride ..].  The split is that of the frame's pred.
 // METRICS = false: the five fit sums.  METRICS = true: the eight metric sums, and with `aligned` the
 // metric depth of every pixel, valid or not.
 template <bool METRICS, bool MASK>
-__global__ __launch_bounds__(kBlock) void eval_partial_kernel(const float* __restrict__ pred,
-                                                              const float* __restrict__ gt,
-                                                              const uint8_t* __restrict__ valid, int64_t S,
-                                                              const float* __restrict__ ss, int ss_per_frame,
-                                                              float max_depth, float* __restrict__ aligned,
-                                                              double* __restrict__ part) {
+__global__ __launch_bounds__(kStreamBlock) void eval_partial_kernel(const float* __restrict__ pred,
+                                                                    const float* __restrict__ gt,
+                                                                    const uint8_t* __restrict__ valid, int64_t S,
+                                                                    const float* __restrict__ ss, int ss_per_frame,
+                                                                    float max_depth, float* __restrict__ aligned,
+                                                                    double* __restrict__ part) {
   constexpr int K = METRICS ? kMetricSums : kFitSums;
   const int64_t f = blockIdx.y;
   const float* pf = pred + f * S;
   const float* gf = gt + f * S;
   const uint8_t* vf = MASK ? valid + f * S : nullptr;
   float* af = (METRICS && aligned) ? aligned + f * S : nullptr;
-  int64_t head = (int64_t)((16 - ((uintptr_t)pf & 15)) & 15) / 4;
-  if (head > S) head = S;
-  const int64_t nvec = (S - head) / 4;
+  const StreamSplit sp = stream_split_f32(pf, S);
   float scale = 1.f, shift = 0.f;
   if (METRICS) {
     const float* sf = ss + (ss_per_frame ? 2 * f : 0);
@@ -146,48 +118,39 @@ __global__ __launch_bounds__(kBlock) void eval_partial_kernel(const float* __res
   for (int j = 0; j < K; ++j) s[j] = 0.;
   int c[4] = {0, 0, 0, 0};  // the counts: four for the metrics, c[0] alone for the fit
 
-  const float* pb = pf + head;
-  const float* gb = gf + head;
-  const uint8_t* vb = MASK ? vf + head : nullptr;
-  const int64_t stride = (int64_t)gridDim.x * kBlock;
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < nvec; i += stride) {
-    const f4 p = *reinterpret_cast<const f4*>(pb + 4 * i);
-    const f4a4 g = *reinterpret_cast<const f4a4*>(gb + 4 * i);
-    bool m[4] = {true, true, true, true};
-    if (MASK) {
-      const u8x4a1 mv = *reinterpret_cast<const u8x4a1*>(vb + 4 * i);
+  stream_walk(
+      S, sp.head, sp.nvec,
+      [&](int64_t o) {
+        const f4 p = *reinterpret_cast<const f4*>(pf + o);
+        const f4a4 g = *reinterpret_cast<const f4a4*>(gf + o);
+        bool m[4] = {true, true, true, true};
+        if (MASK) {
+          const u8x4a1 mv = *reinterpret_cast<const u8x4a1*>(vf + o);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) m[j] = mv[j] != 0;
-    }
-    if constexpr (METRICS) {
-      f4a4 d;
+          for (int j = 0; j < 4; ++j) m[j] = mv[j] != 0;
+        }
+        if constexpr (METRICS) {
+          f4a4 d;
 #pragma unroll
-      for (int j = 0; j < 4; ++j) d[j] = align_metric_depth(p[j], scale, shift, max_depth);
-      if (af) *reinterpret_cast<f4a4*>(af + head + 4 * i) = d;
+          for (int j = 0; j < 4; ++j) d[j] = align_metric_depth(p[j], scale, shift, max_depth);
+          if (af) *reinterpret_cast<f4a4*>(af + o) = d;
 #pragma unroll
-      for (int j = 0; j < 4; ++j) metric_accumulate(s, c, d[j], g[j], m[j]);
-    } else {
+          for (int j = 0; j < 4; ++j) metric_accumulate(s, c, d[j], g[j], m[j]);
+        } else {
 #pragma unroll
-      for (int j = 0; j < 4; ++j) fit_accumulate(s, c[0], p[j], g[j], m[j]);
-    }
-  }
-  if (blockIdx.x == 0) {
-    const int64_t tail0 = head + 4 * nvec;
-    const int tail = (int)(S - tail0);  // 0..3
-    int64_t e = -1;
-    if ((int64_t)threadIdx.x < head) e = threadIdx.x;
-    else if ((int)threadIdx.x >= 8 && (int)threadIdx.x - 8 < tail) e = tail0 + (threadIdx.x - 8);
-    if (e >= 0) {
-      const bool m = MASK ? vf[e] != 0 : true;
-      if constexpr (METRICS) {
-        const float d = align_metric_depth(pf[e], scale, shift, max_depth);
-        if (af) af[e] = d;
-        metric_accumulate(s, c, d, gf[e], m);
-      } else {
-        fit_accumulate(s, c[0], pf[e], gf[e], m);
-      }
-    }
-  }
+          for (int j = 0; j < 4; ++j) fit_accumulate(s, c[0], p[j], g[j], m[j]);
+        }
+      },
+      [&](int64_t e) {
+        const bool m = MASK ? vf[e] != 0 : true;
+        if constexpr (METRICS) {
+          const float d = align_metric_depth(pf[e], scale, shift, max_depth);
+          if (af) af[e] = d;
+          metric_accumulate(s, c, d, gf[e], m);
+        } else {
+          fit_accumulate(s, c[0], pf[e], gf[e], m);
+        }
+      });
   if constexpr (METRICS) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) s[j] = (double)c[j];
@@ -197,41 +160,25 @@ __global__ __launch_bounds__(kBlock) void eval_partial_kernel(const float* __res
   block_store_partial<K>(s, part + (f * gridDim.x + blockIdx.x) * kPartStride);
 }
 
-// One wave per frame: lane l adds the frame's partials l, l + 64, ... in index order, a butterfly adds
-// the lanes, lanes 0..K-1 store out[f * K + j].
+// One wave per frame adds the frame's partials; lanes 0..K-1 store out[f * K + j].
 template <int K>
 __global__ __launch_bounds__(64) void frame_reduce_kernel(const double* __restrict__ part, int nparts,
                                                           double* __restrict__ out) {
   const int64_t f = blockIdx.x;
-  const double* pf = part + f * nparts * kPartStride;
-  double a[K];
-#pragma unroll
-  for (int j = 0; j < K; ++j) a[j] = 0.;
-  for (int b = threadIdx.x; b < nparts; b += 64) {
-#pragma unroll
-    for (int j = 0; j < K; ++j) a[j] += pf[(int64_t)b * kPartStride + j];
-  }
-#pragma unroll
-  for (int j = 0; j < K; ++j) {
-    a[j] = wave_sum_f64(a[j]);
-    if ((int)threadIdx.x == j) out[f * K + j] = a[j];
-  }
+  wave_add_partials<K>(part + f * nparts * kPartStride, nparts, kPartStride, [&](int j, double v) {
+    if ((int)threadIdx.x == j) out[f * K + j] = v;
+  });
 }
 
-// 2x2 normal equations in fp64 (the plain closed form, no contraction), rounded once on the store.
+// (c0, c1) of the 2x2 normal equations to scale = 1 / c0, shift = -c1 / c0, rounded once on the store.
 // No valid pixel (det == 0 with a_11 == 0), det == 0 or c0 == 0 -> (inf, 0).
 __device__ __forceinline__ void fit_solve(const double (&a)[kFitSums], float* __restrict__ ss) {
 #pragma clang fp contract(off)
-  const double a00 = a[0], a01 = a[1], a11 = a[2], b0 = a[3], b1 = a[4];
-  const double det = a00 * a11 - a01 * a01;
+  double c0 = 0., c1 = 0.;
   double scale = __builtin_inf(), shift = 0.;
-  if (det != 0.) {
-    const double c0 = (a11 * b0 - a01 * b1) / det;
-    const double c1 = (-a01 * b0 + a00 * b1) / det;
-    if (c0 != 0.) {
-      scale = 1. / c0;
-      shift = -c1 / c0;
-    }
+  if (solve_2x2(a, c0, c1) && c0 != 0.) {
+    scale = 1. / c0;
+    shift = -c1 / c0;
   }
   ss[0] = (float)scale;
   ss[1] = (float)shift;
@@ -313,12 +260,12 @@ extern "C" int vda_depth_eval_fit(const float* pred, const float* gt, const uint
   const int B = blocks_per_frame(S);
   double* part = (double*)ws;
   double* fsum = part + (int64_t)F * B * kPartStride;
-  const dim3 grid(B, F);
+  const dim3 grid(B, F), block(kStreamBlock);
   if (valid)
-    hipLaunchKernelGGL((eval_partial_kernel<false, true>), grid, dim3(kBlock), 0, (hipStream_t)stream, pred, gt, valid, S,
+    hipLaunchKernelGGL((eval_partial_kernel<false, true>), grid, block, 0, (hipStream_t)stream, pred, gt, valid, S,
                        (const float*)nullptr, 0, 0.f, (float*)nullptr, part);
   else
-    hipLaunchKernelGGL((eval_partial_kernel<false, false>), grid, dim3(kBlock), 0, (hipStream_t)stream, pred, gt, valid, S,
+    hipLaunchKernelGGL((eval_partial_kernel<false, false>), grid, block, 0, (hipStream_t)stream, pred, gt, valid, S,
                        (const float*)nullptr, 0, 0.f, (float*)nullptr, part);
   VDA_LAUNCH_CHECK();
   hipLaunchKernelGGL(frame_reduce_kernel<kFitSums>, dim3(F), dim3(64), 0, (hipStream_t)stream, (const double*)part, B,
@@ -344,12 +291,12 @@ extern "C" int vda_depth_eval_metrics(const float* pred, const float* gt, const 
   VDA_CHECK_ARG(ws_bytes >= vda_depth_eval_workspace(F, S), "workspace smaller than vda_depth_eval_workspace(F, S)");
   const int B = blocks_per_frame(S);
   double* part = (double*)ws;
-  const dim3 grid(B, F);
+  const dim3 grid(B, F), block(kStreamBlock);
   if (valid)
-    hipLaunchKernelGGL((eval_partial_kernel<true, true>), grid, dim3(kBlock), 0, (hipStream_t)stream, pred, gt, valid, S, ss,
+    hipLaunchKernelGGL((eval_partial_kernel<true, true>), grid, block, 0, (hipStream_t)stream, pred, gt, valid, S, ss,
                        ss_per_frame ? 1 : 0, max_depth, aligned, part);
   else
-    hipLaunchKernelGGL((eval_partial_kernel<true, false>), grid, dim3(kBlock), 0, (hipStream_t)stream, pred, gt, valid, S,
+    hipLaunchKernelGGL((eval_partial_kernel<true, false>), grid, block, 0, (hipStream_t)stream, pred, gt, valid, S,
                        ss, ss_per_frame ? 1 : 0, max_depth, aligned, part);
   VDA_LAUNCH_CHECK();
   hipLaunchKernelGGL(frame_reduce_kernel<kMetricSums>, dim3(F), dim3(64), 0, (hipStream_t)stream, (const double*)part, B,

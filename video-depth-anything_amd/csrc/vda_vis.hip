@@ -1,11 +1,10 @@
 // Depth visualisation on the device: the clip-wide min / max and the colour lookup of the reference's
 // save_video (utils/dc_utils.py:74-85), from fp32 depth straight to the bytes that go into the file.
 //
-// range:    depths.min(), depths.max() (dc_utils.py:76) as a two-stage reduction in the manner of
-//           vda_scale_shift: grid-stride with 16-byte loads on the aligned body, per thread -> wave
-//           butterfly -> block in wave order -> per-block partials in the caller's workspace -> one block
-//           reduces the partials.  min / max are order-independent, so the result is exact; NaNs are
-//           skipped (fminf / fmaxf).  HBM-bound: 4 B per element read.
+// range:    depths.min(), depths.max() (dc_utils.py:76) as a streaming pass (vda_stream.h) with 16-byte
+//           loads on depth, a min / max block reduction into per-block partials in the caller's
+//           workspace, and one block that reduces the partials.  min / max are order-independent, so the
+//           result is exact; NaNs are skipped (fminf / fmaxf).  HBM-bound: 4 B per element read.
 // colorize: i = uint8((d - min) / (max - min) * 255) (dc_utils.py:79), every operation one correctly
 //           rounded fp32 operation as numpy float32 computes it (IEEE division, no rcp, no contraction),
 //           then out = lut[i] in one of four layouts.  The host path makes about eight full-size passes,
@@ -14,41 +13,27 @@
 //           conflicts depend on the data (neighbouring pixels of a depth map mostly share an index, which
 //           broadcasts, or hit neighbouring entries, which lie on different banks).
 // Stores are dwords: frames and planes start at f * H * W and c * H * W bytes, which are not multiples
-// of 4 in general, so every plane has its own head (the bytes before its first dword boundary), body
-// (groups of 4 pixels, one dword per plane, three dwords for interleaved RGB) and tail, as vda_eval.hip
-// has for pred; the depth loads of the body are element-aligned 16-byte loads.  Planes whose heads differ
+// of 4 in general, so every plane is a streaming pass of its own (vda_stream.h, split by the dword rule
+// on the destination): head, body (groups of 4 pixels, one dword per plane, three dwords for interleaved
+// RGB) and tail; the depth loads of the body are element-aligned 16-byte loads.  Planes whose heads differ
 // (planar 4:4:4 with H * W % 4 != 0) are written in one pass per plane.  4:2:0: a thread owns a strip of
 // four 2x2 blocks (8 x 2 pixels): it looks every pixel up once, stores the luma of both rows and the two
 // averaged chroma dwords; a strip whose row address is not dword-aligned, or that is cut by the right
 // edge, goes out in the widest aligned stores its address allows (bytes and 16-bit words around dwords;
 // none of that at W % 8 == 0 with a dword-aligned output).
-#include "vda_common.h"
+#include "vda_stream.h"
 #include "../../include/vda.h"
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kWaves = kBlock / 64;
 constexpr int kMaxFrames = 65535;  // grid.y
-// range: a block takes kRangeIters 16-byte groups per thread while n is large enough
-constexpr int64_t kRangeIters = 4;
-constexpr int64_t kRangeSpan = (int64_t)kBlock * 4 * kRangeIters;
-constexpr int64_t kRangeMaxBlocks = 1024;
-// colorize: pixels per block and pass while the frame is large enough; at most kMaxBlocksPerFrame blocks
-constexpr int64_t kColorSpan = (int64_t)kBlock * 4 * 4;
-constexpr int64_t kMaxBlocksPerFrame = 512;
+// range: a block takes 4 16-byte groups per thread while n is large enough; at most 1,024 blocks
+int range_grid(int64_t n) { return stream_grid(n, kStreamGroup * 4, 1024); }
+// colorize: 4 groups of 4 pixels per thread and pass while the frame is large enough; at most 512 blocks
+// per frame
+int color_grid(int64_t S) { return stream_grid(S, kStreamGroup * 4, 512); }
 
 typedef uint32_t u32x3a4 __attribute__((ext_vector_type(3), aligned(4)));
-
-int range_grid(int64_t n) {
-  const int64_t want = (n + kRangeSpan - 1) / kRangeSpan;
-  return (int)(want < 1 ? 1 : (want > kRangeMaxBlocks ? kRangeMaxBlocks : want));
-}
-
-int color_grid(int64_t S) {
-  const int64_t want = (S + kColorSpan - 1) / kColorSpan;
-  return (int)(want < 1 ? 1 : (want > kMaxBlocksPerFrame ? kMaxBlocksPerFrame : want));
-}
 
 __device__ __forceinline__ float wave_min(float v) {
 #pragma unroll
@@ -58,7 +43,7 @@ __device__ __forceinline__ float wave_min(float v) {
 
 // The block's (min, max) to out[0], out[1]: waves through LDS, thread 0 stores.
 __device__ __forceinline__ void block_store_range(float mn, float mx, float* __restrict__ out) {
-  __shared__ float red[kWaves][2];
+  __shared__ float red[kStreamWaves][2];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   mn = wave_min(mn);
   mx = wave_max(mx);
@@ -69,7 +54,7 @@ __device__ __forceinline__ void block_store_range(float mn, float mx, float* __r
   __syncthreads();
   if (threadIdx.x == 0) {
 #pragma unroll
-    for (int w = 1; w < kWaves; ++w) {
+    for (int w = 1; w < kStreamWaves; ++w) {
       mn = fminf(mn, red[w][0]);
       mx = fmaxf(mx, red[w][1]);
     }
@@ -78,39 +63,32 @@ __device__ __forceinline__ void block_store_range(float mn, float mx, float* __r
   }
 }
 
-// head = elements before depth's first 16-byte boundary, nvec = 16-byte groups after it; block 0 also
-// takes the head and the tail.  part [gridDim.x, 2].
-__global__ __launch_bounds__(kBlock) void range_partial_kernel(const float* __restrict__ depth, int64_t n, int head,
-                                                               int64_t nvec, float* __restrict__ part) {
+// The split is depth's.  part [gridDim.x, 2].
+__global__ __launch_bounds__(kStreamBlock) void range_partial_kernel(const float* __restrict__ depth, int64_t n,
+                                                                     float* __restrict__ part) {
   float mn = __builtin_inff(), mx = -__builtin_inff();
-  const float* db = depth + head;
-  const int64_t stride = (int64_t)gridDim.x * kBlock;
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < nvec; i += stride) {
-    const f4 d = *reinterpret_cast<const f4*>(db + 4 * i);
+  const StreamSplit sp = stream_split_f32(depth, n);
+  stream_walk(
+      n, sp.head, sp.nvec,
+      [&](int64_t o) {
+        const f4 d = *reinterpret_cast<const f4*>(depth + o);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      mn = fminf(mn, d[j]);
-      mx = fmaxf(mx, d[j]);
-    }
-  }
-  if (blockIdx.x == 0) {
-    const int64_t tail0 = head + 4 * nvec;
-    const int tail = (int)(n - tail0);  // 0..3
-    int64_t e = -1;
-    if ((int)threadIdx.x < head) e = threadIdx.x;
-    else if ((int)threadIdx.x >= 8 && (int)threadIdx.x - 8 < tail) e = tail0 + (threadIdx.x - 8);
-    if (e >= 0) {
-      mn = fminf(mn, depth[e]);
-      mx = fmaxf(mx, depth[e]);
-    }
-  }
+        for (int j = 0; j < 4; ++j) {
+          mn = fminf(mn, d[j]);
+          mx = fmaxf(mx, d[j]);
+        }
+      },
+      [&](int64_t e) {
+        mn = fminf(mn, depth[e]);
+        mx = fmaxf(mx, depth[e]);
+      });
   block_store_range(mn, mx, part + 2 * (int64_t)blockIdx.x);
 }
 
-__global__ __launch_bounds__(kBlock) void range_final_kernel(const float* __restrict__ part, int nparts,
-                                                             float* __restrict__ range) {
+__global__ __launch_bounds__(kStreamBlock) void range_final_kernel(const float* __restrict__ part, int nparts,
+                                                                   float* __restrict__ range) {
   float mn = __builtin_inff(), mx = -__builtin_inff();
-  for (int b = threadIdx.x; b < nparts; b += kBlock) {
+  for (int b = threadIdx.x; b < nparts; b += kStreamBlock) {
     mn = fminf(mn, part[2 * b]);
     mx = fmaxf(mx, part[2 * b + 1]);
   }
@@ -141,83 +119,63 @@ template <int NPL, bool IDX>
 __device__ __forceinline__ void planes_pass(const float* __restrict__ df, int64_t S, float lo, float den,
                                             const uint32_t* tab, uint8_t* __restrict__ dst, int64_t pstride,
                                             int sel0) {
-  int64_t head = (int64_t)((4 - ((uintptr_t)dst & 3)) & 3);
-  if (head > S) head = S;
-  const int64_t nvec = (S - head) / 4;
-  const float* db = df + head;
-  uint8_t* ob = dst + head;
-  const int64_t stride = (int64_t)gridDim.x * kBlock;
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < nvec; i += stride) {
-    const f4a4 d = *reinterpret_cast<const f4a4*>(db + 4 * i);
-    uint32_t v[4];
+  const StreamSplit sp = stream_split_u8(dst, 1, S);
+  stream_walk(
+      S, sp.head, sp.nvec,
+      [&](int64_t o) {
+        const f4a4 d = *reinterpret_cast<const f4a4*>(df + o);
+        uint32_t v[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const uint32_t k = depth_index(d[j], lo, den);
-      v[j] = IDX ? k : tab[k] >> (8 * sel0);
-    }
+        for (int j = 0; j < 4; ++j) {
+          const uint32_t k = depth_index(d[j], lo, den);
+          v[j] = IDX ? k : tab[k] >> (8 * sel0);
+        }
 #pragma unroll
-    for (int c = 0; c < NPL; ++c) {
-      const uint32_t w = ((v[0] >> (8 * c)) & 0xffu) | (((v[1] >> (8 * c)) & 0xffu) << 8) |
-                         (((v[2] >> (8 * c)) & 0xffu) << 16) | (((v[3] >> (8 * c)) & 0xffu) << 24);
-      *reinterpret_cast<uint32_t*>(ob + c * pstride + 4 * i) = w;
-    }
-  }
-  if (blockIdx.x == 0) {
-    const int64_t tail0 = head + 4 * nvec;
-    const int tail = (int)(S - tail0);  // 0..3
-    int64_t e = -1;
-    if ((int64_t)threadIdx.x < head) e = threadIdx.x;
-    else if ((int)threadIdx.x >= 8 && (int)threadIdx.x - 8 < tail) e = tail0 + (threadIdx.x - 8);
-    if (e >= 0) {
-      const uint32_t k = depth_index(df[e], lo, den);
-      const uint32_t v = IDX ? k : tab[k] >> (8 * sel0);
+        for (int c = 0; c < NPL; ++c) {
+          const uint32_t w = ((v[0] >> (8 * c)) & 0xffu) | (((v[1] >> (8 * c)) & 0xffu) << 8) |
+                             (((v[2] >> (8 * c)) & 0xffu) << 16) | (((v[3] >> (8 * c)) & 0xffu) << 24);
+          *reinterpret_cast<uint32_t*>(dst + c * pstride + o) = w;
+        }
+      },
+      [&](int64_t e) {
+        const uint32_t k = depth_index(df[e], lo, den);
+        const uint32_t v = IDX ? k : tab[k] >> (8 * sel0);
 #pragma unroll
-      for (int c = 0; c < NPL; ++c) dst[c * pstride + e] = (uint8_t)(v >> (8 * c));
-    }
-  }
+        for (int c = 0; c < NPL; ++c) dst[c * pstride + e] = (uint8_t)(v >> (8 * c));
+      });
 }
 
-// Interleaved rows: pixel p of the frame at dst + 3 p.  The head is (dst & 3) pixels (3 h = -h mod 4), a
-// group of 4 pixels is 12 bytes = three dwords.
+// Interleaved rows: pixel p of the frame at dst + 3 p.  A group of 4 pixels is 12 bytes = three dwords.
 __device__ __forceinline__ void hwc_pass(const float* __restrict__ df, int64_t S, float lo, float den,
                                          const uint32_t* tab, uint8_t* __restrict__ dst) {
-  int64_t head = (int64_t)((uintptr_t)dst & 3);
-  if (head > S) head = S;
-  const int64_t nvec = (S - head) / 4;
-  const float* db = df + head;
-  uint8_t* ob = dst + 3 * head;
-  const int64_t stride = (int64_t)gridDim.x * kBlock;
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < nvec; i += stride) {
-    const f4a4 d = *reinterpret_cast<const f4a4*>(db + 4 * i);
-    uint32_t v[4];
+  const StreamSplit sp = stream_split_u8(dst, 3, S);
+  stream_walk(
+      S, sp.head, sp.nvec,
+      [&](int64_t o) {
+        const f4a4 d = *reinterpret_cast<const f4a4*>(df + o);
+        uint32_t v[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = tab[depth_index(d[j], lo, den)];  // the top byte is 0
-    u32x3a4 w;
-    w[0] = v[0] | (v[1] << 24);
-    w[1] = (v[1] >> 8) | (v[2] << 16);
-    w[2] = (v[2] >> 16) | (v[3] << 8);
-    *reinterpret_cast<u32x3a4*>(ob + 12 * i) = w;
-  }
-  if (blockIdx.x == 0) {
-    const int64_t tail0 = head + 4 * nvec;
-    const int tail = (int)(S - tail0);  // 0..3
-    int64_t e = -1;
-    if ((int64_t)threadIdx.x < head) e = threadIdx.x;
-    else if ((int)threadIdx.x >= 8 && (int)threadIdx.x - 8 < tail) e = tail0 + (threadIdx.x - 8);
-    if (e >= 0) {
-      const uint32_t v = tab[depth_index(df[e], lo, den)];
-      dst[3 * e] = (uint8_t)v;
-      dst[3 * e + 1] = (uint8_t)(v >> 8);
-      dst[3 * e + 2] = (uint8_t)(v >> 16);
-    }
-  }
+        for (int j = 0; j < 4; ++j) v[j] = tab[depth_index(d[j], lo, den)];  // the top byte is 0
+        u32x3a4 w;
+        w[0] = v[0] | (v[1] << 24);
+        w[1] = (v[1] >> 8) | (v[2] << 16);
+        w[2] = (v[2] >> 16) | (v[3] << 8);
+        *reinterpret_cast<u32x3a4*>(dst + 3 * o) = w;
+      },
+      [&](int64_t e) {
+        const uint32_t v = tab[depth_index(df[e], lo, den)];
+        dst[3 * e] = (uint8_t)v;
+        dst[3 * e + 1] = (uint8_t)(v >> 8);
+        dst[3 * e + 2] = (uint8_t)(v >> 16);
+      });
 }
 
 // Frame f = blockIdx.y; the frame's pixels are spread over gridDim.x blocks.
 template <int LAYOUT>
-__global__ __launch_bounds__(kBlock) void colorize_kernel(const float* __restrict__ depth, int64_t S,
-                                                          const float* __restrict__ range,
-                                                          const uint8_t* __restrict__ lut, uint8_t* __restrict__ out) {
+__global__ __launch_bounds__(kStreamBlock) void colorize_kernel(const float* __restrict__ depth, int64_t S,
+                                                                const float* __restrict__ range,
+                                                                const uint8_t* __restrict__ lut,
+                                                                uint8_t* __restrict__ out) {
   __shared__ uint32_t tab[256];
   if (LAYOUT != VDA_VIS_INDEX) stage_table(lut, tab);
   const int64_t f = blockIdx.y;
@@ -267,10 +225,10 @@ __device__ __forceinline__ void store_strip(uint8_t* p, uint64_t v, int n) {
 // 4:2:0: unit u of a frame is the strip of chroma row cy = u / ns, chroma columns 4 g .. 4 g + 3
 // (g = u % ns, ns = ceil(cw / 4)): pixels [2 cy, 2 cy + 1] x [8 g, 8 g + 7], rows and columns past the
 // edge repeating the last one.
-__global__ __launch_bounds__(kBlock) void colorize_420_kernel(const float* __restrict__ depth, int H, int W,
-                                                              const float* __restrict__ range,
-                                                              const uint8_t* __restrict__ lut,
-                                                              uint8_t* __restrict__ out) {
+__global__ __launch_bounds__(kStreamBlock) void colorize_420_kernel(const float* __restrict__ depth, int H, int W,
+                                                                    const float* __restrict__ range,
+                                                                    const uint8_t* __restrict__ lut,
+                                                                    uint8_t* __restrict__ out) {
   __shared__ uint32_t tab[256];
   stage_table(lut, tab);
   const int64_t S = (int64_t)H * W;
@@ -285,8 +243,8 @@ __global__ __launch_bounds__(kBlock) void colorize_420_kernel(const float* __res
   const float den = range[1] - lo;
   const int64_t ns = (cw + 3) / 4;
   const int64_t units = (int64_t)ch * ns;
-  const int64_t stride = (int64_t)gridDim.x * kBlock;
-  for (int64_t u = (int64_t)blockIdx.x * kBlock + threadIdx.x; u < units; u += stride) {
+  const int64_t stride = (int64_t)gridDim.x * kStreamBlock;
+  for (int64_t u = (int64_t)blockIdx.x * kStreamBlock + threadIdx.x; u < units; u += stride) {
     const int cy = (int)(u / ns);
     const int g = (int)(u - (int64_t)cy * ns);
     const int x0 = 8 * g, y0 = 2 * cy;
@@ -356,14 +314,11 @@ extern "C" int vda_depth_range(const float* depth, int64_t n, float* range, void
                 "depth, range and the workspace must be 4-byte aligned");
   VDA_CHECK_ARG(ws_bytes >= vda_depth_range_workspace(n), "workspace smaller than vda_depth_range_workspace(n)");
   const int grid = range_grid(n);
-  int64_t head = (int64_t)((16 - ((uintptr_t)depth & 15)) & 15) / 4;
-  if (head > n) head = n;
-  const int64_t nvec = (n - head) / 4;
   float* part = (float*)ws;
-  hipLaunchKernelGGL(range_partial_kernel, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, depth, n, (int)head, nvec,
-                     part);
+  hipLaunchKernelGGL(range_partial_kernel, dim3(grid), dim3(kStreamBlock), 0, (hipStream_t)stream, depth, n, part);
   VDA_LAUNCH_CHECK();
-  hipLaunchKernelGGL(range_final_kernel, dim3(1), dim3(kBlock), 0, (hipStream_t)stream, (const float*)part, grid, range);
+  hipLaunchKernelGGL(range_final_kernel, dim3(1), dim3(kStreamBlock), 0, (hipStream_t)stream, (const float*)part, grid,
+                     range);
   VDA_LAUNCH_CHECK();
   return 0;
 }
@@ -392,20 +347,20 @@ extern "C" int vda_depth_colorize(const float* depth, int32_t F, int32_t H, int3
   VDA_CHECK_ARG(((uintptr_t)depth & 3) == 0 && ((uintptr_t)range & 3) == 0, "depth and range must be 4-byte aligned");
   const int64_t S = (int64_t)H * W;
   const hipStream_t st = (hipStream_t)stream;
-  const dim3 grid(color_grid(S), F);
+  const dim3 grid(color_grid(S), F), block(kStreamBlock);
   switch (layout) {
     case VDA_VIS_INDEX:
-      hipLaunchKernelGGL(colorize_kernel<VDA_VIS_INDEX>, grid, dim3(kBlock), 0, st, depth, S, range, lut, out);
+      hipLaunchKernelGGL(colorize_kernel<VDA_VIS_INDEX>, grid, block, 0, st, depth, S, range, lut, out);
       break;
     case VDA_VIS_HWC:
-      hipLaunchKernelGGL(colorize_kernel<VDA_VIS_HWC>, grid, dim3(kBlock), 0, st, depth, S, range, lut, out);
+      hipLaunchKernelGGL(colorize_kernel<VDA_VIS_HWC>, grid, block, 0, st, depth, S, range, lut, out);
       break;
     case VDA_VIS_PLANAR444:
-      hipLaunchKernelGGL(colorize_kernel<VDA_VIS_PLANAR444>, grid, dim3(kBlock), 0, st, depth, S, range, lut, out);
+      hipLaunchKernelGGL(colorize_kernel<VDA_VIS_PLANAR444>, grid, block, 0, st, depth, S, range, lut, out);
       break;
     default:  // a thread takes 16 pixels, so a quarter of the blocks
-      hipLaunchKernelGGL(colorize_420_kernel, dim3(color_grid((S + 3) / 4), F), dim3(kBlock), 0, st, depth, H, W, range,
-                         lut, out);
+      hipLaunchKernelGGL(colorize_420_kernel, dim3(color_grid((S + 3) / 4), F), block, 0, st, depth, H, W, range, lut,
+                         out);
       break;
   }
   VDA_LAUNCH_CHECK();
