@@ -462,12 +462,15 @@ def test_halo_cout128_product_route(H, W, relu):
     note(f"halo Cout 128 {H}x{W}", worst)
 
 
-@pytest.mark.parametrize("Hs,Ws,H,W", [(1, 1, 16, 16), (9, 9, 17, 17), (8, 20, 33, 47), (16, 16, 16, 16)])
+@pytest.mark.parametrize("Hs,Ws,H,W", [(1, 1, 16, 16), (9, 9, 17, 17), (8, 20, 33, 47), (16, 16, 16, 16),
+                                       (22, 21, 33, 33), (21, 22, 33, 33), (22, 22, 33, 33)])
 def test_halo_fused_resize_edges(Hs, Ws, H, W):
     """3x3 conv (Cout = 128) on a bilinear resize fused into the halo conv's patch staging: from one pixel, x2
     with a ragged tile, a ragged non-integer ratio.  The identity 16 x 16 -> 16 x 16 is the case
     vda_conv_halo_fused DECLINES (a tile's source window of 20 x 20 pixels exceeds its 192-pixel staging), so
-    it runs on vda_launch_conv_reg and must still be correct.  The resized operand is an fp16 rounding."""
+    it runs on vda_launch_conv_reg and must still be correct.  To 33 x 33 (scale (Hs - 1) / 32, exact) the
+    staging boundary itself: 22 x 21 and 21 x 22 need 14 x 13 = 182 pixels (served), 22 x 22 needs 196
+    (declined).  The resized operand is an fp16 rounding."""
     c = bias_case(2, 64, 128, Hs, Ws, True, Hs + W, up=(H, W))
     _, worst = run_conv(c, {}, False, f"fused resize {Hs}x{Ws}->{H}x{W}", product=True)
     note(f"halo fused resize {Hs}x{Ws}->{H}x{W}", worst)

@@ -461,6 +461,63 @@ def test_depth_head_edges(C, Hin, Win, Ho, Wo, BT):
     note(what + f" (implicit GEMM forced {w13:.3f})", worst)
 
 
+# To 33 x 33 the scale is (Hs - 1) / 32, exact in fp32.  A 16 x 16 tile stages a source window of at most
+# (int)(17 sy) + 3 rows x (int)(17 sx) + 3 columns in a 192-pixel slot: 22 x 21 and 21 x 22 give 14 x 13 = 182
+# pixels (served), 22 x 22 gives 14 x 14 = 196 (declined).  The served shapes put a 13 x 12 = 156-pixel window in
+# the second tile (y0 = 16: source rows 9..21).
+STAGING_OUT = 33
+STAGING_CASES = [(22, 21, True), (21, 22, True), (22, 22, False)]
+
+
+def staging_case(C, Hs, Ws, BT):
+    x, w1, b1, w2, b2 = fb.depth_head_case(C, Hs, Ws, BT, seed=C + Hs * Ws)
+    hi, lo = fb.split_hi_lo(w1.permute(0, 2, 3, 1).contiguous())
+    args = (torch.cat([hi, lo], 0).to(DEV).contiguous(), f32(b1), f32(w2), f32(b2), STAGING_OUT, STAGING_OUT)
+    return (x, w1, b1, w2, b2), h(x.permute(0, 2, 3, 1)), args
+
+
+@pytest.mark.parametrize("BT", [1, 2])
+@pytest.mark.parametrize("Hs,Ws,served", STAGING_CASES)
+def test_depth_head_staging_boundary(Hs, Ws, served, BT):
+    """Both sides of the one predicate (halo_fused_fits) that decides whether the depth conv builds its patches
+    from a staged source window, and with it the depth head's workspace: C = 32, no workspace where served and
+    the resized map where declined; the output within the bound, bit for bit the materialised resize + the same
+    conv (tuning build, dconv = 2), and nothing stored outside it."""
+    C, S = 32, STAGING_OUT
+    case, xh, args = staging_case(C, Hs, Ws, BT)
+    ref, bound = fb.depth_head_ref_bound(*case, S, S)
+    what = f"depth tail staging C={C} {Hs}x{Ws}->{S}x{S} BT={BT}"
+    assert lib().vda_depth_head_workspace(BT, Hs, Ws, C, S, S) == (0 if served else BT * S * S * C * 2), what
+    buf, y = c_depth_head(lib(), xh, *args)
+    worst = assert_elementwise(y, ref, bound, what)
+    assert guard_ok(buf), f"{what}: a store outside the output"
+    T = tune_lib()
+    with T.route(dconv=2):
+        buf2, y2 = c_depth_head(T.lib, xh, *args)
+    assert torch.equal(y, y2), f"{what}: differs from resize + conv"
+    assert guard_ok(buf2)
+    note(what, worst)
+
+
+@pytest.mark.parametrize("BT", [1, 2])
+@pytest.mark.parametrize("Hs,Ws,served", STAGING_CASES)
+def test_depth_head_staging_boundary_halo(Hs, Ws, served, BT):
+    """The same boundary on the 8-wave halo route (tuning build, dconv = 0) at C = 64: its workspace, and the
+    fused output bit for bit the materialised one (force_tile = 9)."""
+    C, S = 64, STAGING_OUT
+    _, xh, args = staging_case(C, Hs, Ws, BT)
+    what = f"depth tail staging (halo) C={C} {Hs}x{Ws}->{S}x{S} BT={BT}"
+    T = tune_lib()
+    with T.route(dconv=0):
+        assert T.depth_head_workspace(BT, Hs, Ws, C, S, S) == (0 if served else BT * S * S * C * 2), what
+        buf, y = c_depth_head(T.lib, xh, *args)
+        with T.route(force_tile=9):
+            assert T.depth_head_workspace(BT, Hs, Ws, C, S, S) == BT * S * S * C * 2
+            buf2, y2 = c_depth_head(T.lib, xh, *args)
+    assert torch.equal(y, y2), f"{what}: differs from resize + conv"
+    assert guard_ok(buf) and guard_ok(buf2), f"{what}: a store outside the output"
+
+
 @pytest.mark.parametrize("C,Hin,Win,Ho,Wo", [(64, 8, 20, 33, 47), (64, 37, 37, 19, 19), (40, 9, 9, 15, 17)])
 def test_depth_head_nan_frame_isolation(C, Hin, Win, Ho, Wo):
     x, w1, b1, w2, b2 = fb.depth_head_case(C, Hin, Win, 1, seed=C)

@@ -157,6 +157,6 @@ for name in shapes:
             e1.record()
             torch.cuda.synchronize()
             times[li].append(e0.elapsed_time(e1) / 3 * 1e3)
-    line = f"{name:6s}: " + " | ".join(f"{os.path.basename(os.path.dirname(p))}: med {statistics.median(t):7.1f}us min {min(t):7.1f}us "
+    line = f"{name:6s}: " + " | ".join(f"{os.path.basename(os.path.dirname(p))}: med {statistics.median(t):7.1f}us min {min(t):7.1f}us max {max(t):7.1f}us "
                                       f"{fl / statistics.median(t) / 1e6:6.1f}TF" for p, t in zip(libs, times))
     print(line + f" | bit-identical {same}", flush=True)

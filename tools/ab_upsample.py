@@ -44,7 +44,7 @@ def main():
         same = torch.equal(outs[0], outs[1])
         line = f"{BT}x{H}x{W}x{C} -> {Ho}x{Wo}:"
         for p, t in zip(args.libs, times):
-            line += f" | {p.split('/')[-2]}: med {statistics.median(t):.1f}us min {min(t):.1f}us"
+            line += f" | {p.split('/')[-2]}: med {statistics.median(t):.1f}us min {min(t):.1f}us max {max(t):.1f}us"
         print(line + f" | bit-identical [{same}]", flush=True)
 
 

@@ -64,6 +64,18 @@ __device__ __forceinline__ float erf_fast(float x) {
 // bits whatever the compiler's contraction choice in its code shape (a restructured loop could keep the
 // rounded product instead and move w by an ulp: DESIGN.md §3, round-4 levers).
 __device__ __forceinline__ float ac_weight(float sc, float o, int i0) { return __builtin_fmaf(sc, o, -(float)i0); }
+// The align_corners=True source scale (in - 1) / (out - 1), 0 for out == 1 (torch upsample_bilinear2d), and
+// the source pair and weight of output coordinate o at that scale.  The one definition of each: every
+// resize site, device or host, forms its scale and its (i0, i1, w) here, hoisting the scale itself.
+__host__ __device__ __forceinline__ float ac_scale(int in, int out) {
+  return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f;
+}
+__device__ __forceinline__ void ac_coord(int o, int in, float sc, int& i0, int& i1, float& w) {
+  const float f = sc * (float)o;
+  i0 = (int)f;
+  i1 = min(i0 + 1, in - 1);
+  w = ac_weight(sc, (float)o, i0);
+}
 
 __device__ __forceinline__ h8 bilerp8(h8 a, h8 b, h8 c, h8 d, float wx, float wy) {
   const float ux = 1.f - wx, uy = 1.f - wy;
@@ -123,8 +135,7 @@ __device__ __forceinline__ uint4 bilerp8_mix(uint4 a, uint4 b, uint4 c, uint4 d,
 // behind vda_depth_resize and vda_depth_align, so the two cannot drift.
 __device__ __forceinline__ float depth_bilinear_ac(const float* __restrict__ f, int H, int W, int ho, int wo, int oy,
                                                    int ox) {
-  const float ry = ho > 1 ? (float)(H - 1) / (float)(ho - 1) : 0.f;
-  const float rx = wo > 1 ? (float)(W - 1) / (float)(wo - 1) : 0.f;
+  const float ry = ac_scale(H, ho), rx = ac_scale(W, wo);
   const float sy = ry * (float)oy, sx = rx * (float)ox;
   const int y0 = (int)sy, x0 = (int)sx;
   const int y1 = y0 + (y0 < H - 1 ? 1 : 0), x1 = x0 + (x0 < W - 1 ? 1 : 0);

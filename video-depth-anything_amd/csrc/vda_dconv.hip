@@ -25,6 +25,7 @@
 // read while tap t's MFMAs run.  Both layouts are conflict-free for the ds_read_b128 lane groups at
 // any tap offset (16 consecutive pixels / rows, chunks c and c + 1).
 #include "vda_internal.h"
+#include "vda_halo.h"
 
 namespace {
 
@@ -34,29 +35,22 @@ constexpr int DC_PP = (DC_NPIX * 4 + 63) / 64;  // 21 one-KiB pieces per patch s
 constexpr int DC_PPW = (DC_PP + 3) / 4;         // per wave, at most (6)
 constexpr int DC_PSLOT = DC_PP * 512;           // halfs
 constexpr int DC_WROW = 3 * 64 * 32;            // halfs of one phase's W (3 taps x 64 rows x 32 channels)
-constexpr int DC_SRCP = 12;                     // UPS: 1-KiB pieces of the source-region slot (192 pixels)
+constexpr int DC_SRCP = HALO_SRC_PIXELS * 4 / 64;  // UPS: 1-KiB pieces of the source-region slot (4 chunks a pixel)
 constexpr int DC_SSLOT = DC_SRCP * 512;         // halfs
+static_assert(DC_SRCP * 64 == HALO_SRC_PIXELS * 4 && DC_SRCP == 4 * 3, "source slot: 3 pieces per wave (src_dma)");
 
-
-template <int N>
-__device__ __forceinline__ void dc_wait() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 __device__ __forceinline__ void dc_wait_n(int n) {  // n: wave-uniform, 0..9
-  if (n >= 9) dc_wait<9>();
-  else if (n == 8) dc_wait<8>();
-  else if (n == 7) dc_wait<7>();
-  else if (n == 6) dc_wait<6>();
-  else if (n == 5) dc_wait<5>();
-  else if (n == 4) dc_wait<4>();
-  else if (n == 3) dc_wait<3>();
-  else if (n == 2) dc_wait<2>();
-  else if (n == 1) dc_wait<1>();
-  else dc_wait<0>();
+  if (n >= 9) wait_vmcnt<9>();
+  else if (n == 8) wait_vmcnt<8>();
+  else if (n == 7) wait_vmcnt<7>();
+  else if (n == 6) wait_vmcnt<6>();
+  else if (n == 5) wait_vmcnt<5>();
+  else if (n == 4) wait_vmcnt<4>();
+  else if (n == 3) wait_vmcnt<3>();
+  else if (n == 2) wait_vmcnt<2>();
+  else if (n == 1) wait_vmcnt<1>();
+  else wait_vmcnt<0>();
 }
-// lgkmcnt(0) as the builtin (vmcnt / expcnt untouched): the compiler then knows the fragments read
-// before it are complete and adds no wait of its own for them after later reads
-__device__ __forceinline__ void dc_lgkm0() { __builtin_amdgcn_s_waitcnt(0xC07F); }
 
 // UPS: U is the map BEFORE the bilinear (align_corners=True) resize from (Hs, Ws) to (H, W); each
 // unit's patch is interpolated in LDS from a staged source region (bilerp8, the resize kernel's
@@ -91,11 +85,7 @@ __global__ __launch_bounds__(256, 2) void depth_conv_kernel(const h16* __restric
   const int my_pp = (DC_PP - 1 - wave) / 4 + 1;  // patch pieces of this wave (6 or 5)
 
   auto tile_of = [&](int i, int& bt, int& y0, int& x0) {  // i-th tile of this block
-    const int t = blockIdx.x + i * gridDim.x;
-    const int tx = t % tiles_x, r = t / tiles_x;
-    y0 = (r % tiles_y) * DC_T;
-    x0 = tx * DC_T;
-    bt = r / tiles_y;
+    halo_tile_of(blockIdx.x + i * gridDim.x, tiles_x, tiles_y, DC_T, bt, y0, x0);
   };
   // Per-lane constants, computed once (no per-phase division or 64-bit address math):
   //  patch piece j (q = wave + 4 j): this lane's pixel row / column in the patch and source chunk
@@ -143,13 +133,9 @@ __global__ __launch_bounds__(256, 2) void depth_conv_kernel(const h16* __restric
     }
   };
   // UPS: source region of unit u's patch: rows sy_lo .. sy_lo + SR - 1, columns sx_lo .. + SC - 1
-  const float usy = (UPS && H > 1) ? (float)(Hs - 1) / (float)(H - 1) : 0.f;
-  const float usx = (UPS && W > 1) ? (float)(Ws - 1) / (float)(W - 1) : 0.f;
+  const float usy = UPS ? ac_scale(Hs, H) : 0.f, usx = UPS ? ac_scale(Ws, W) : 0.f;
   auto src_region = [&](int y0, int x0, int& sy_lo, int& sx_lo, int& SR, int& SC) {
-    sy_lo = (int)(usy * (float)max(y0 - 1, 0));
-    sx_lo = (int)(usx * (float)max(x0 - 1, 0));
-    SR = min((int)(usy * (float)min(y0 + DC_T, H - 1)) + 1, Hs - 1) - sy_lo + 1;
-    SC = min((int)(usx * (float)min(x0 + DC_T, W - 1)) + 1, Ws - 1) - sx_lo + 1;
+    halo_src_region(usy, usx, y0, x0, DC_T, H, W, Hs, Ws, sy_lo, sx_lo, SR, SC);
   };
   // this wave's 3 source pieces (q = 3 wave + j: pixels 16 q .. + 15 of the SR x SC region, 4 chunks
   // each, unswizzled) of unit u -> the source slot
@@ -170,12 +156,9 @@ __global__ __launch_bounds__(256, 2) void depth_conv_kernel(const h16* __restric
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (VDA_LDS void*)(ssm + q * 512), 16, (int)vo, slab * 64, 0, 0);
     }
   };
-  // interpolate unit u's patch from the source slot into patch slot (u & 1) (padding pixels -> 0),
-  // separably: bilerp8_mix's blend is o = fma(wy, bot, uy * top) with top / bot the horizontal blends
-  // fma(wx, B, ux * A) of source rows sy0 / sy1 at the output column, and a source row's horizontal
-  // blend at a column does not depend on the output row that uses it, so each is formed once per
-  // (column, source row) and carried down the column: the same ops, bit-identical to bilerp8_mix per
-  // pixel (and so to vda_upsample_bilinear), in ~45 % of its VALU.
+  // interpolate unit u's patch from the source slot into patch slot (u & 1) (padding pixels -> 0) with
+  // halo_blend_column: bit-identical to bilerp8_mix per pixel (and so to vda_upsample_bilinear), in
+  // ~45 % of its VALU.
   // Thread = (column px_l, channel chunk c, 6-row segment): waves 0..2 own columns 0..15 of segment
   // `wave` (the row, hence sy0 / sy1 / wy, is wave-uniform), lanes 0..23 of wave 3 columns 16, 17.
   auto interp_sep = [&](int u) {
@@ -187,56 +170,13 @@ __global__ __launch_bounds__(256, 2) void depth_conv_kernel(const h16* __restric
     const int seg = w3 ? lane >> 3 : wave;
     const int px_l = w3 ? 16 + ((lane >> 2) & 1) : lane >> 2, c = lane & 3;
     if (w3 && lane >= 24) return;
-    const int pxg = x0 - 1 + px_l;
-    const bool okx = (unsigned)pxg < (unsigned)W;
-    const float ox = (float)min(max(pxg, 0), W - 1);
-    const int sx0 = (int)(usx * ox), sx1 = min(sx0 + 1, Ws - 1);
-    const float wx = ac_weight(usx, ox, sx0), ux = 1.f - wx;
-    const int c0 = sx0 - sx_lo, c1 = sx1 - sx_lo;
-    auto hrow = [&](int sy, float (&t)[8]) {
-      const int r = (sy - sy_lo) * SC;
-      const uint4 a = *reinterpret_cast<const uint4*>(ssm + ((r + c0) * 4 + c) * 8);
-      const uint4 b = *reinterpret_cast<const uint4*>(ssm + ((r + c1) * 4 + c) * 8);
-      const unsigned A[4] = {a.x, a.y, a.z, a.w}, B[4] = {b.x, b.y, b.z, b.w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        t[2 * j] = fma_mix_lo(wx, B[j], fma_mix_lo(ux, A[j], -0.f));
-        t[2 * j + 1] = fma_mix_hi(wx, B[j], fma_mix_hi(ux, A[j], -0.f));
-      }
-    };
-    float top[8], bot[8];
-    int s0 = -1, s1 = -1;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-      const int pr = seg * 6 + k;
-      const int pyg = y0 - 1 + pr;
-      const float oy = (float)min(max(pyg, 0), H - 1);
-      const int sy0 = (int)(usy * oy), sy1 = min(sy0 + 1, Hs - 1);
-      const float wy = ac_weight(usy, oy, sy0), uy = 1.f - wy;
-      if (sy0 != s0) {  // scale <= 1: the source rows advance by at most one per output row
-        if (sy0 == s1) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) top[e] = bot[e];
-        } else {
-          hrow(sy0, top);
-        }
-        hrow(sy1, bot);
-        s0 = sy0;
-        s1 = sy1;
-      }
-      unsigned o[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float ol = fma_f32(wy, bot[2 * j], mul_f32(uy, top[2 * j]));
-        const float oh = fma_f32(wy, bot[2 * j + 1], mul_f32(uy, top[2 * j + 1]));
-        typedef float f2v __attribute__((ext_vector_type(2)));
-        o[j] = __builtin_bit_cast(unsigned, __builtin_convertvector(f2v{ol, oh}, h2));
-      }
-      const bool ok = okx && (unsigned)pyg < (unsigned)H;
-      const uint4 v = ok ? make_uint4(o[0], o[1], o[2], o[3]) : make_uint4(0u, 0u, 0u, 0u);
-      const int p = pr * DC_P + px_l;
-      *reinterpret_cast<uint4*>(psm + (u & 1) * DC_PSLOT + (p * 4 + (c ^ ((p >> 1) & 3))) * 8) = v;
-    }
+    halo_blend_column<6>(
+        usy, usx, y0, x0, px_l, seg * 6, H, W, Hs, Ws, sy_lo, sx_lo,
+        [&](int r, int col) { return *reinterpret_cast<const uint4*>(ssm + ((r * SC + col) * 4 + c) * 8); },
+        [&](int pr, uint4 v) {
+          const int p = pr * DC_P + px_l;
+          *reinterpret_cast<uint4*>(psm + (u & 1) * DC_PSLOT + (p * 4 + (c ^ ((p >> 1) & 3))) * 8) = v;
+        });
   };
   // this wave's 3 pieces of phase g's W slice (kernel row dy = g % 3 of unit g / 3) -> slot g % 3
   auto w_dma = [&](int g) {
@@ -259,10 +199,10 @@ __global__ __launch_bounds__(256, 2) void depth_conv_kernel(const h16* __restric
     // prologue: unit 0's source region -> its patch (interpolated), W(0); unit 1's source in flight
     src_dma(0);
     w_dma(0);
-    dc_wait<0>();
+    wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
     interp_sep(0);
-    dc_lgkm0();
+    lgkm0();
     __builtin_amdgcn_s_barrier();
     if (my_units > 1) src_dma(1);
   } else {
@@ -271,9 +211,9 @@ __global__ __launch_bounds__(256, 2) void depth_conv_kernel(const h16* __restric
     w_dma(0);
     if (G > 1) {
       w_dma(1);
-      dc_wait<3>();
+      wait_vmcnt<3>();
     } else {
-      dc_wait<0>();
+      wait_vmcnt<0>();
     }
   }
 
@@ -355,19 +295,19 @@ __global__ __launch_bounds__(256, 2) void depth_conv_kernel(const h16* __restric
     const h16* wb = wsm + (g % DC_WRING) * DC_WROW;
     h8 xa[4], wa[4], xb[4], wb2[4];
     read_tap(ps, wb, dy, 0, xa, wa);
-    dc_lgkm0();
+    lgkm0();
     __builtin_amdgcn_sched_barrier(0);
     read_tap(ps, wb, dy, 1, xb, wb2);
     __builtin_amdgcn_sched_barrier(0);
     mfma_tap(xa, wa);
     __builtin_amdgcn_sched_barrier(0);
-    dc_lgkm0();
+    lgkm0();
     __builtin_amdgcn_sched_barrier(0);
     read_tap(ps, wb, dy, 2, xa, wa);
     __builtin_amdgcn_sched_barrier(0);
     mfma_tap(xb, wb2);
     __builtin_amdgcn_sched_barrier(0);
-    dc_lgkm0();
+    lgkm0();
     __builtin_amdgcn_sched_barrier(0);
     mfma_tap(xa, wa);
     __builtin_amdgcn_sched_barrier(0);
@@ -407,7 +347,7 @@ __global__ __launch_bounds__(256, 2) void depth_conv_kernel(const h16* __restric
       // with the source staged in row 0, measured 3 % slower: the source fetch then has one phase)
       if (dy == 1 && u + 1 < my_units) {
         interp_sep(u + 1);
-        dc_lgkm0();
+        lgkm0();
       }
       // W(g + 1) (issued this phase) must have landed before barrier g + 1; so must, at row 0, the
       // source region of unit u + 1 (issued in row 2 of unit u - 1).  Newer: row 2's source pieces
@@ -450,38 +390,31 @@ bool vda_depth_conv_serves(int H, int W, int C) { return C % 32 == 0 && C > 0 &&
 int vda_depth_conv(const void* U, const void* w1, const float* b1, const float* w2, const float* b2, float* depth,
                    int BT, int H, int W, int C, hipStream_t st) {
   if (!vda_depth_conv_serves(H, W, C)) return 1;
-  const int cus = vda_cu_count();
-  const int tiles_x = (W + DC_T - 1) / DC_T, tiles_y = (H + DC_T - 1) / DC_T;
-  const long nt = (long)BT * tiles_x * tiles_y;
-  if (nt > 0x7fffffffL / 9 / ((C + 31) / 32)) return vda_set_error(-22, "depth conv: too many tiles");
-  const int ntiles = (int)nt;
-  const int grid = ntiles < 2 * cus ? ntiles : 2 * cus;
-  hipLaunchKernelGGL(depth_conv_kernel<false>, dim3(grid), dim3(256), 0, st, (const h16*)U, (const h16*)w1, b1, w2, b2,
-                     depth, H, W, C, tiles_x, tiles_y, ntiles, H, W);
+  HaloGrid g;  // two blocks per CU
+  if (!halo_tile_grid(BT, H, W, DC_T, 2, 0x7fffffffL / 9 / ((C + 31) / 32), g))
+    return vda_set_error(-22, "depth conv: too many tiles");
+  hipLaunchKernelGGL(depth_conv_kernel<false>, dim3(g.grid), dim3(256), 0, st, (const h16*)U, (const h16*)w1, b1, w2, b2,
+                     depth, H, W, C, g.tiles_x, g.tiles_y, g.ntiles, H, W);
   VDA_LAUNCH_CHECK();
   return 0;
 }
 
 // the same on the UN-resized map x [BT, Hs, Ws, C] (Hs <= H, Ws <= W): the bilinear resize is computed
 // while each patch is built (bit-identical to vda_upsample_bilinear + vda_depth_conv); the staged
-// source region of a tile (<= floor(17 * scale) + 3 pixels per side) must fit 192 pixels.
+// source region of a tile must fit the source slot (halo_fused_fits).
 bool vda_depth_conv_fused_serves(int Hs, int Ws, int H, int W, int C) {
   if (!vda_depth_conv_serves(H, W, C) || g_dconv_mode == 2 || Hs > H || Ws > W || Hs < 1 || Ws < 1) return false;
-  const float sy = H > 1 ? (float)(Hs - 1) / (float)(H - 1) : 0.f, sx = W > 1 ? (float)(Ws - 1) / (float)(W - 1) : 0.f;
-  return ((int)(17.f * sy) + 3) * ((int)(17.f * sx) + 3) <= 192;
+  return halo_fused_fits(Hs, Ws, H, W);
 }
 
 int vda_depth_conv_fused(const void* x, const void* w1, const float* b1, const float* w2, const float* b2,
                          float* depth, int BT, int Hs, int Ws, int H, int W, int C, hipStream_t st) {
   if (!vda_depth_conv_fused_serves(Hs, Ws, H, W, C)) return 1;
-  const int cus = vda_cu_count();
-  const int tiles_x = (W + DC_T - 1) / DC_T, tiles_y = (H + DC_T - 1) / DC_T;
-  const long nt = (long)BT * tiles_x * tiles_y;
-  if (nt > 0x7fffffffL / 9 / ((C + 31) / 32)) return vda_set_error(-22, "depth conv: too many tiles");
-  const int ntiles = (int)nt;
-  const int grid = ntiles < 2 * cus ? ntiles : 2 * cus;
-  hipLaunchKernelGGL(depth_conv_kernel<true>, dim3(grid), dim3(256), 0, st, (const h16*)x, (const h16*)w1, b1, w2, b2,
-                     depth, H, W, C, tiles_x, tiles_y, ntiles, Hs, Ws);
+  HaloGrid g;  // two blocks per CU
+  if (!halo_tile_grid(BT, H, W, DC_T, 2, 0x7fffffffL / 9 / ((C + 31) / 32), g))
+    return vda_set_error(-22, "depth conv: too many tiles");
+  hipLaunchKernelGGL(depth_conv_kernel<true>, dim3(g.grid), dim3(256), 0, st, (const h16*)x, (const h16*)w1, b1, w2, b2,
+                     depth, H, W, C, g.tiles_x, g.tiles_y, g.ntiles, Hs, Ws);
   VDA_LAUNCH_CHECK();
   return 0;
 }

@@ -19,6 +19,7 @@
 // 16 B) resp. ^((pixel >> 1) & 3) (CPX = 4); weights row*CPX + (chunk ^ ((row >> 1) & (CPX-1))):
 // conflict-free for the ds_read_b128 lane groups at any patch offset (brute-forced).
 #include "vda_internal.h"
+#include "vda_halo.h"
 
 namespace {
 
@@ -31,14 +32,7 @@ constexpr int DT = 16;              // output tile edge
 constexpr int DP = DT + 2;          // patch edge (halo 1)
 constexpr int DNPIX = DP * DP;      // 324
 
-__device__ __forceinline__ void dh_glds16(const void* src, h16* lds_base) {
-  __builtin_amdgcn_global_load_lds(src, (VDA_LDS void*)lds_base, 16, 0, 0);
-}
 typedef unsigned dh_u4 __attribute__((ext_vector_type(4)));
-template <int N>
-__device__ __forceinline__ void dh_wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 template <int CPX>
 __device__ __forceinline__ int patch_pos(int p, int cd) {
@@ -48,17 +42,6 @@ __device__ __forceinline__ int patch_pos(int p, int cd) {
 template <int CPX>
 __device__ __forceinline__ int w_pos(int n, int cd) {
   return cd ^ ((n >> 1) & (CPX - 1));
-}
-// align_corners=True source coordinate, as vda_upsample_bilinear computes it (torch upsample_bilinear2d);
-// sc = (in - 1) / (out - 1) (0 for out == 1) is hoisted out by the caller, same float division
-__device__ __forceinline__ float dh_ac_scale(int in, int out) {
-  return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f;
-}
-__device__ __forceinline__ void dh_ac_coord(int o, int in, float sc, int& i0, int& i1, float& w) {
-  const float f = sc * (float)o;
-  i0 = (int)f;
-  i1 = min(i0 + 1, in - 1);
-  w = ac_weight(sc, (float)o, i0);
 }
 
 // DEPTH: the depth tail (64 weight rows = 32 hi + 32 lo, wave n-blocks {ng, ng+2}, ReLU/1x1/ReLU epilogue
@@ -104,8 +87,9 @@ __global__ __launch_bounds__(512 + 64 * IW) void halo_conv_kernel(const h16* __r
   constexpr int WRING = 2;                               // weight ring
   static_assert(!UPS || 9 / TPS >= 2, "UPS: >= 2 steps per unit");
   static_assert(IW == 0 || (UPS && TPS == 1), "interpolation waves: the 9-step fused-resize conv");
-  constexpr int SPPW = (192 * CPX + 511) / 512;          // UPS source pieces per wave (fixed count)
-  constexpr int SSLOT = UPS ? SPPW * 8 * 64 : 0;         // source slots: >= 192 pixels x CPX chunks
+  constexpr int SPPW = (HALO_SRC_PIXELS * CPX + 511) / 512;  // UPS source pieces per wave (fixed count)
+  constexpr int SSLOT = UPS ? SPPW * 8 * 64 : 0;         // source slots: every pixel halo_fused_fits admits
+  static_assert(SPPW * 8 * 64 >= HALO_SRC_PIXELS * CPX, "source slot: HALO_SRC_PIXELS pixels x CPX chunks");
   __shared__ __attribute__((aligned(16))) h16 dsm[2 * PBUF + WRING * WBUF + SSLOT * 8 + 512];
   h16* patch = dsm;                                      // [2][PBUF]
   h16* wbuf = dsm + 2 * PBUF;                            // [WRING][WBUF]
@@ -130,13 +114,7 @@ __global__ __launch_bounds__(512 + 64 * IW) void halo_conv_kernel(const h16* __r
   // a unit's coordinates are formed once (the divisions are scalar but long), not per DMA piece
   struct Ud { int bt, y0, x0, slab, sy_lo, sx_lo, SR, SC; };
   auto tile_of_unit = [&](int u, int& bt, int& y0, int& x0) {
-    const int t = blockIdx.x + (u / units_per_tile) * gridDim.x;
-    const int tx = t % tiles_x;
-    const int r = t / tiles_x;
-    const int ty = r % tiles_y;
-    bt = r / tiles_y;
-    y0 = ty * DT;
-    x0 = tx * DT;
+    halo_tile_of(blockIdx.x + (u / units_per_tile) * gridDim.x, tiles_x, tiles_y, DT, bt, y0, x0);
   };
   // piece q of unit u's patch slab -> ring slot (u & 1)
   auto dma_patch = [&](int u, const Ud& ud, int q) {
@@ -149,25 +127,20 @@ __global__ __launch_bounds__(512 + 64 * IW) void halo_conv_kernel(const h16* __r
     const void* src = zero;
     if (p < DNPIX && pos < CPX && (unsigned)py < (unsigned)H && (unsigned)px < (unsigned)W)
       src = U + (((long)bt * H + py) * W + px) * C + slab * SLAB + cd * 8;
-    dh_glds16(src, patch + (u & 1) * PBUF + q * 512);
+    glds16(src, patch + (u & 1) * PBUF + q * 512);
   };
   // weight pieces of global step gs (kernel row dy of slab) -> ring slot (gs & 1)
-  // UPS: source region of unit u's patch: rows sy_lo .. sy_lo + SR - 1, columns sx_lo .. + SC - 1
+  // UPS: a unit's Ud holds the source region of its patch (halo_src_region): rows sy_lo .. sy_lo + SR - 1,
+  // columns sx_lo .. + SC - 1
   constexpr int USL = DNPIX * CPX;                       // 16-B patch slots read by the taps
   constexpr int UCH = UPS ? (USL + 511) / 512 : 1;       // patch slots per thread
-  const float usy = UPS ? dh_ac_scale(Hs, H) : 0.f, usx = UPS ? dh_ac_scale(Ws, W) : 0.f;
-  auto src_region = [&](int y0, int x0, int& sy_lo, int& sx_lo, int& SR, int& SC) {
-    sy_lo = (int)(usy * (float)max(y0 - 1, 0));
-    sx_lo = (int)(usx * (float)max(x0 - 1, 0));
-    SR = min((int)(usy * (float)min(y0 + DT, H - 1)) + 1, Hs - 1) - sy_lo + 1;
-    SC = min((int)(usx * (float)min(x0 + DT, W - 1)) + 1, Ws - 1) - sx_lo + 1;
-  };
+  const float usy = UPS ? ac_scale(Hs, H) : 0.f, usx = UPS ? ac_scale(Ws, W) : 0.f;
   auto make_ud = [&](int u) {
     Ud ud;
     tile_of_unit(u, ud.bt, ud.y0, ud.x0);
     ud.slab = u % units_per_tile;
     ud.sy_lo = ud.sx_lo = ud.SR = ud.SC = 0;
-    if constexpr (UPS) src_region(ud.y0, ud.x0, ud.sy_lo, ud.sx_lo, ud.SR, ud.SC);
+    if constexpr (UPS) halo_src_region(usy, usx, ud.y0, ud.x0, DT, H, W, Hs, Ws, ud.sy_lo, ud.sx_lo, ud.SR, ud.SC);
     return ud;
   };
   // piece j (of SPPW) of unit u's source region -> sbuf; slot = pixel * CPX + chunk
@@ -178,7 +151,7 @@ __global__ __launch_bounds__(512 + 64 * IW) void halo_conv_kernel(const h16* __r
     const int r = px / SC, c = px - r * SC;
     const void* src = zero;
     if (r < SR) src = U + (((long)bt * Hs + sy_lo + r) * Ws + sx_lo + c) * C + slab * SLAB + cd * 8;
-    dh_glds16(src, sbuf + q * 512);
+    glds16(src, sbuf + q * 512);
   };
   // interpolate unit u's patch from sbuf into patch ring slot (u & 1); padding pixels -> 0
   // slots t0 + k * tstride (k < NK) of the patch (t0 = this thread's first)
@@ -196,8 +169,8 @@ __global__ __launch_bounds__(512 + 64 * IW) void halo_conv_kernel(const h16* __r
       const bool ok = (unsigned)py < (unsigned)H && (unsigned)px < (unsigned)W;
       int sy0, sy1, sx0, sx1;
       float wy, wx;
-      dh_ac_coord(min(max(py, 0), H - 1), Hs, usy, sy0, sy1, wy);
-      dh_ac_coord(min(max(px, 0), W - 1), Ws, usx, sx0, sx1, wx);
+      ac_coord(min(max(py, 0), H - 1), Hs, usy, sy0, sy1, wy);
+      ac_coord(min(max(px, 0), W - 1), Ws, usx, sx0, sx1, wx);
       const int r0 = (sy0 - sy_lo) * SC, r1 = (sy1 - sy_lo) * SC, c0 = sx0 - sx_lo, c1 = sx1 - sx_lo;
       const h8 a = *reinterpret_cast<const h8*>(sbuf + ((r0 + c0) * CPX + cd) * 8);
       const h8 b = *reinterpret_cast<const h8*>(sbuf + ((r0 + c1) * CPX + cd) * 8);
@@ -214,75 +187,26 @@ __global__ __launch_bounds__(512 + 64 * IW) void halo_conv_kernel(const h16* __r
                      "v"(__builtin_bit_cast(dh_u4, o))
                      : "memory");
     }
-    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the stores above are invisible to the compiler's counts
+    lgkm0();  // the stores above are invisible to the compiler's counts
   };
   // The interpolation waves' form of ups_interp (LIN layout): item = (patch column, channel chunk,
-  // 6-row segment).  The blend is o = fma(wy, bot, uy * top) with top / bot the horizontal blends
-  // fma(wx, B, ux * A) of source rows sy0 / sy1 at the column; a source row's horizontal blend at a
-  // column does not depend on the output row that uses it, so it is formed once per (column, source
-  // row) and carried down the segment: per pixel the ops of bilerp8_mix (bit-identical to bilerp8, the
-  // resize kernel's blend) in about half its VALU.
+  // ISEG-row segment) of halo_blend_column, stored with the asm ds_write_b128 (as above)
   constexpr int ISEG = 3;                                // rows per item (6: 1809, 9: 1966 vs 1781 us)
   constexpr int NITEM = (DP / ISEG) * DP * CPX;          // 432 for a 64-channel slab
   auto ups_interp_item = [&](int u, const Ud& ud, int it) {
     if (it >= NITEM) return;
-    const int y0 = ud.y0, x0 = ud.x0, sy_lo = ud.sy_lo, sx_lo = ud.sx_lo, SC = ud.SC;
+    const int SC = ud.SC;
     const int cd = it % CPX, col = (it / CPX) % DP, seg = it / (CPX * DP);
-    const int pxg = x0 - 1 + col;
-    const bool okx = (unsigned)pxg < (unsigned)W;
-    int sx0, sx1;
-    float wx;
-    dh_ac_coord(min(max(pxg, 0), W - 1), Ws, usx, sx0, sx1, wx);
-    const float ux = 1.f - wx;
-    const int c0 = sx0 - sx_lo, c1 = sx1 - sx_lo;
-    auto hrow = [&](int sy, float (&t)[8]) {
-      const int r = (sy - sy_lo) * SC;
-      const uint4 a = *reinterpret_cast<const uint4*>(sbuf + ((r + c0) * CPX + cd) * 8);
-      const uint4 b = *reinterpret_cast<const uint4*>(sbuf + ((r + c1) * CPX + cd) * 8);
-      const unsigned A[4] = {a.x, a.y, a.z, a.w}, B[4] = {b.x, b.y, b.z, b.w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        t[2 * j] = fma_mix_lo(wx, B[j], fma_mix_lo(ux, A[j], -0.f));
-        t[2 * j + 1] = fma_mix_hi(wx, B[j], fma_mix_hi(ux, A[j], -0.f));
-      }
-    };
-    float top[8], bot[8];
-    int s0 = -1, s1 = -1;
-#pragma unroll
-    for (int k = 0; k < ISEG; ++k) {
-      const int pr = seg * ISEG + k;
-      const int pyg = y0 - 1 + pr;
-      int sy0, sy1;
-      float wy;
-      dh_ac_coord(min(max(pyg, 0), H - 1), Hs, usy, sy0, sy1, wy);
-      const float uy = 1.f - wy;
-      if (sy0 != s0) {  // scale <= 1: the source rows advance by at most one per output row
-        if (sy0 == s1) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) top[e] = bot[e];
-        } else {
-          hrow(sy0, top);
-        }
-        hrow(sy1, bot);
-        s0 = sy0;
-        s1 = sy1;
-      }
-      unsigned o[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float ol = fma_f32(wy, bot[2 * j], mul_f32(uy, top[2 * j]));
-        const float oh = fma_f32(wy, bot[2 * j + 1], mul_f32(uy, top[2 * j + 1]));
-        typedef float f2v __attribute__((ext_vector_type(2)));
-        o[j] = __builtin_bit_cast(unsigned, __builtin_convertvector(f2v{ol, oh}, h2));
-      }
-      const bool ok = okx && (unsigned)pyg < (unsigned)H;
-      const dh_u4 v = ok ? dh_u4{o[0], o[1], o[2], o[3]} : dh_u4{0u, 0u, 0u, 0u};
-      const int slot = (pr * DP + col) * PSTR + cd;
-      asm volatile("ds_write_b128 %0, %1" ::"v"((unsigned)(uintptr_t)(VDA_LDS h16*)(patch + (u & 1) * PBUF + slot * 8)),
-                   "v"(v)
-                   : "memory");
-    }
-    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the asm stores are invisible to the compiler's counts
+    halo_blend_column<ISEG>(
+        usy, usx, ud.y0, ud.x0, col, seg * ISEG, H, W, Hs, Ws, ud.sy_lo, ud.sx_lo,
+        [&](int r, int c) { return *reinterpret_cast<const uint4*>(sbuf + ((r * SC + c) * CPX + cd) * 8); },
+        [&](int pr, uint4 v) {
+          const int slot = (pr * DP + col) * PSTR + cd;
+          asm volatile("ds_write_b128 %0, %1" ::"v"((unsigned)(uintptr_t)(VDA_LDS h16*)(patch + (u & 1) * PBUF + slot * 8)),
+                       "v"(__builtin_bit_cast(dh_u4, v))
+                       : "memory");
+        });
+    lgkm0();  // the asm stores are invisible to the compiler's counts
   };
   // weight pieces of step st of a unit of slab `slab` -> ring slot `wslot`
   auto dma_w = [&](int st, int slab, int wslot) {
@@ -293,7 +217,7 @@ __global__ __launch_bounds__(512 + 64 * IW) void halo_conv_kernel(const h16* __r
       const int n = s / WROW, rem = s - n * WROW;
       const int tt = rem / CPX, pos = rem - tt * CPX;
       const int cd = w_pos<CPX>(n, pos);
-      dh_glds16(w1 + (long)n * K + (st * TPS + tt) * C + slab * SLAB + cd * 8, wbuf + wslot * WBUF + piece * 512);
+      glds16(w1 + (long)n * K + (st * TPS + tt) * C + slab * SLAB + cd * 8, wbuf + wslot * WBUF + piece * 512);
     }
   };
 
@@ -304,14 +228,14 @@ __global__ __launch_bounds__(512 + 64 * IW) void halo_conv_kernel(const h16* __r
       for (int j = 0; j < SPPW; ++j) dma_src(ud_next, wave + j * 8);
       dma_w(0, ud_next.slab, 0);
     }
-    dh_wait_vmcnt<0>();
+    wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
     if (!iwave) ups_interp(0, ud_next, tid, 512, std::integral_constant<int, UCH>{});
     __syncthreads();  // patch slot 0 written, source slot free for unit 1
   } else {
     for (int q = wave; q < PP; q += 8) dma_patch(0, ud_next, q);
     dma_w(0, ud_next.slab, 0);
-    dh_wait_vmcnt<0>();
+    wait_vmcnt<0>();
   }
   __builtin_amdgcn_s_barrier();
 
@@ -334,7 +258,7 @@ __global__ __launch_bounds__(512 + 64 * IW) void halo_conv_kernel(const h16* __r
           for (int j = SPI / 2; j < SPI; ++j) dma_src(ud_next, (wave - 8) + j * IW);
         if (ist >= 3 && ist < 3 + ISTEPS && iu + 1 < my_units)
           ups_interp_item(iu + 1, ud_next, (ist - 3) * 64 * IW + (tid - 512));
-        if (ist == 2) dh_wait_vmcnt<0>();
+        if (ist == 2) wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();
         if (++ist == SPU) {
           ist = 0;
@@ -529,14 +453,14 @@ __global__ __launch_bounds__(512 + 64 * IW) void halo_conv_kernel(const h16* __r
     const unsigned long long ts_pre = __builtin_amdgcn_s_memtime();
 #endif
     if constexpr (UPS) {
-      if (IW == 0 && issue_p) dh_wait_vmcnt<SPPW>();
-      else if (IW > 0 && tile_end) dh_wait_vmcnt<NB / 2 * 4>();  // the next step's weights, not the tile's stores
-      else dh_wait_vmcnt<0>();
+      if (IW == 0 && issue_p) wait_vmcnt<SPPW>();
+      else if (IW > 0 && tile_end) wait_vmcnt<NB / 2 * 4>();  // the next step's weights, not the tile's stores
+      else wait_vmcnt<0>();
     } else if (issue_p) {
-      if (my_pp == PPMAX) dh_wait_vmcnt<PPMAX>();
-      else dh_wait_vmcnt<PPMAX - 1>();
+      if (my_pp == PPMAX) wait_vmcnt<PPMAX>();
+      else wait_vmcnt<PPMAX - 1>();
     } else {
-      dh_wait_vmcnt<0>();
+      wait_vmcnt<0>();
     }
     __builtin_amdgcn_s_barrier();
 #ifdef VDA_TS
@@ -591,18 +515,14 @@ extern "C" int vda_debug_oc1_timestamps(void* host) {
 int vda_depth_halo(const void* U, const void* w1, const float* b1, const float* w2, const float* b2, float* depth,
                    int BT, int H, int W, int C, hipStream_t st) {
   if (!(C == 32 || C % 64 == 0)) return 1;
-  const int cus = vda_cu_count();
-  const int tiles_x = (W + DT - 1) / DT, tiles_y = (H + DT - 1) / DT;
-  const long nt = (long)BT * tiles_x * tiles_y;
-  if (nt > 0x7fffffffL) return vda_set_error(-22, "depth head: too many tiles");
-  const int ntiles = (int)nt;
-  const int grid = ntiles < cus ? ntiles : cus;
+  HaloGrid g;
+  if (!halo_tile_grid(BT, H, W, DT, 1, 0x7fffffffL, g)) return vda_set_error(-22, "depth head: too many tiles");
   if (C == 32)
-    hipLaunchKernelGGL((halo_conv_kernel<32, 64, 3, true>), dim3(grid), dim3(512), 0, st, (const h16*)U, (const h16*)w1,
-                       b1, w2, b2, depth, (h16*)nullptr, 0, H, W, C, tiles_x, tiles_y, ntiles);
+    hipLaunchKernelGGL((halo_conv_kernel<32, 64, 3, true>), dim3(g.grid), dim3(512), 0, st, (const h16*)U, (const h16*)w1,
+                       b1, w2, b2, depth, (h16*)nullptr, 0, H, W, C, g.tiles_x, g.tiles_y, g.ntiles);
   else
-    hipLaunchKernelGGL((halo_conv_kernel<64, 64, 3, true>), dim3(grid), dim3(512), 0, st, (const h16*)U, (const h16*)w1,
-                       b1, w2, b2, depth, (h16*)nullptr, 0, H, W, C, tiles_x, tiles_y, ntiles);
+    hipLaunchKernelGGL((halo_conv_kernel<64, 64, 3, true>), dim3(g.grid), dim3(512), 0, st, (const h16*)U, (const h16*)w1,
+                       b1, w2, b2, depth, (h16*)nullptr, 0, H, W, C, g.tiles_x, g.tiles_y, g.ntiles);
   VDA_LAUNCH_CHECK();
   return 0;
 }
@@ -612,22 +532,16 @@ int vda_depth_halo(const void* U, const void* w1, const float* b1, const float* 
 // (2.2 GB at ViT-L 32x518^2) is never written.  Returns 1 when the shape is not served.
 bool vda_depth_halo_fused_serves(int Hs, int Ws, int H, int W, int C) {
   if (C % 64 != 0 || Hs > H || Ws > W || Hs < 1 || Ws < 1) return false;
-  // the staged source region of a tile (<= floor(17 * scale) + 2 rows / columns) must fit 192 pixels
-  const float sy = H > 1 ? (float)(Hs - 1) / (float)(H - 1) : 0.f, sx = W > 1 ? (float)(Ws - 1) / (float)(W - 1) : 0.f;
-  return ((int)(17.f * sy) + 3) * ((int)(17.f * sx) + 3) <= 192;
+  return halo_fused_fits(Hs, Ws, H, W);
 }
 
 int vda_depth_halo_fused(const void* x, const void* w1, const float* b1, const float* w2, const float* b2,
                          float* depth, int BT, int Hs, int Ws, int H, int W, int C, hipStream_t st) {
   if (!vda_depth_halo_fused_serves(Hs, Ws, H, W, C)) return 1;
-  const int cus = vda_cu_count();
-  const int tiles_x = (W + DT - 1) / DT, tiles_y = (H + DT - 1) / DT;
-  const long nt = (long)BT * tiles_x * tiles_y;
-  if (nt > 0x7fffffffL) return vda_set_error(-22, "depth head: too many tiles");
-  const int ntiles = (int)nt;
-  const int grid = ntiles < cus ? ntiles : cus;
-  hipLaunchKernelGGL((halo_conv_kernel<64, 64, 3, true, true>), dim3(grid), dim3(512), 0, st, (const h16*)x,
-                     (const h16*)w1, b1, w2, b2, depth, (h16*)nullptr, 0, H, W, C, tiles_x, tiles_y, ntiles, Hs, Ws);
+  HaloGrid g;
+  if (!halo_tile_grid(BT, H, W, DT, 1, 0x7fffffffL, g)) return vda_set_error(-22, "depth head: too many tiles");
+  hipLaunchKernelGGL((halo_conv_kernel<64, 64, 3, true, true>), dim3(g.grid), dim3(512), 0, st, (const h16*)x,
+                     (const h16*)w1, b1, w2, b2, depth, (h16*)nullptr, 0, H, W, C, g.tiles_x, g.tiles_y, g.ntiles, Hs, Ws);
   VDA_LAUNCH_CHECK();
   return 0;
 }
@@ -639,18 +553,13 @@ int vda_conv_halo_fused(const void* x, const void* w, void* y, const float* bias
                         int H, int W, int Cin, int Cout, hipStream_t st) {
   if (Cout != 128 || Cin % 64 != 0 || Hs > H || Ws > W || Hs < 1 || Ws < 1) return 1;
   if ((long)H * W * Cout * 2 >= (1L << 31)) return 1;  // the epilogue's per-frame buffer stores take 32-bit offsets
-  const float sy = H > 1 ? (float)(Hs - 1) / (float)(H - 1) : 0.f, sx = W > 1 ? (float)(Ws - 1) / (float)(W - 1) : 0.f;
-  if (((int)(17.f * sy) + 3) * ((int)(17.f * sx) + 3) > 192) return 1;
-  const int cus = vda_cu_count();
-  const int tiles_x = (W + DT - 1) / DT, tiles_y = (H + DT - 1) / DT;
-  const long nt = (long)BT * tiles_x * tiles_y;
-  if (nt > 0x7fffffffL) return vda_set_error(-22, "conv: too many tiles");
-  const int ntiles = (int)nt;
-  const int grid = ntiles < cus ? ntiles : cus;
+  if (!halo_fused_fits(Hs, Ws, H, W)) return 1;
+  HaloGrid g;
+  if (!halo_tile_grid(BT, H, W, DT, 1, 0x7fffffffL, g)) return vda_set_error(-22, "conv: too many tiles");
   // 4 interpolation waves (1 / 2: 2571 / 2080 vs 1801 us, profiles/r05_ab_oc1_interp_waves_dconv_separable.log)
-  hipLaunchKernelGGL((halo_conv_kernel<64, 128, 1, false, true, 4>), dim3(grid), dim3(768), 0, st, (const h16*)x,
+  hipLaunchKernelGGL((halo_conv_kernel<64, 128, 1, false, true, 4>), dim3(g.grid), dim3(768), 0, st, (const h16*)x,
                      (const h16*)w, bias, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, (h16*)y, relu,
-                     H, W, Cin, tiles_x, tiles_y, ntiles, Hs, Ws);
+                     H, W, Cin, g.tiles_x, g.tiles_y, g.ntiles, Hs, Ws);
   VDA_LAUNCH_CHECK();
   return 0;
 }
@@ -662,15 +571,11 @@ int vda_conv_halo(const void* x, const void* w, void* y, const float* bias, int 
                   int Cout, hipStream_t st) {
   if (Cout != 128 || Cin % 64 != 0) return 1;
   if ((long)H * W * Cout * 2 >= (1L << 31)) return 1;  // the epilogue's per-frame buffer stores take 32-bit offsets
-  const int cus = vda_cu_count();
-  const int tiles_x = (W + DT - 1) / DT, tiles_y = (H + DT - 1) / DT;
-  const long nt = (long)BT * tiles_x * tiles_y;
-  if (nt > 0x7fffffffL) return vda_set_error(-22, "conv: too many tiles");
-  const int ntiles = (int)nt;
-  const int grid = ntiles < cus ? ntiles : cus;
-  hipLaunchKernelGGL((halo_conv_kernel<64, 128, 1, false>), dim3(grid), dim3(512), 0, st, (const h16*)x, (const h16*)w,
+  HaloGrid g;
+  if (!halo_tile_grid(BT, H, W, DT, 1, 0x7fffffffL, g)) return vda_set_error(-22, "conv: too many tiles");
+  hipLaunchKernelGGL((halo_conv_kernel<64, 128, 1, false>), dim3(g.grid), dim3(512), 0, st, (const h16*)x, (const h16*)w,
                      bias, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, (h16*)y, relu, H, W, Cin,
-                     tiles_x, tiles_y, ntiles);
+                     g.tiles_x, g.tiles_y, g.ntiles);
   VDA_LAUNCH_CHECK();
   return 0;
 }

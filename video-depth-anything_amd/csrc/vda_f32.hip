@@ -430,8 +430,7 @@ __global__ __launch_bounds__(256) void upsample_f32_kernel(const float* __restri
                                                            int H, int W, int C, int Ho, int Wo) {
   const int nc = C >> 2;
   const long total = (long)BT * Ho * Wo * nc;
-  const float ry = Ho > 1 ? (float)(H - 1) / (float)(Ho - 1) : 0.f;
-  const float rx = Wo > 1 ? (float)(W - 1) / (float)(Wo - 1) : 0.f;
+  const float ry = ac_scale(H, Ho), rx = ac_scale(W, Wo);
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
     const int c = (int)(i % nc);
     long t = i / nc;

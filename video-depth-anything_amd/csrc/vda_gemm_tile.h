@@ -14,6 +14,7 @@
 // ds_read_b128 fragment reads bank-conflict free.  gemm_kernel: see its own comment below.
 #pragma once
 #include "vda_internal.h"
+#include "vda_halo.h"
 
 namespace {
 
@@ -69,12 +70,10 @@ struct ConvLoader {
     if (p.up_h > 0) {
       // conv input = bilinear(align_corners=True) upsample of the stored [H, W] map to [up_h, up_w]
       if (iy < 0 || iy >= p.up_h || ix < 0 || ix >= p.up_w) return make_uint4(0, 0, 0, 0);
-      float sy = p.up_h > 1 ? (float)(p.H - 1) / (float)(p.up_h - 1) : 0.f;
-      float sx = p.up_w > 1 ? (float)(p.W - 1) / (float)(p.up_w - 1) : 0.f;
-      float fy = sy * iy, fx = sx * ix;
-      int y0 = (int)fy, x0 = (int)fx;
-      int y1 = min(y0 + 1, p.H - 1), x1 = min(x0 + 1, p.W - 1);
-      float wy = ac_weight(sy, (float)iy, y0), wx = ac_weight(sx, (float)ix, x0);
+      int y0, y1, x0, x1;
+      float wy, wx;
+      ac_coord(iy, p.H, ac_scale(p.H, p.up_h), y0, y1, wy);
+      ac_coord(ix, p.W, ac_scale(p.W, p.up_w), x0, x1, wx);
       const h16* base = p.x + (long)bt[i] * p.H * p.W * p.Cin + ci;
       h8 a = __builtin_bit_cast(h8, ldg16(base + ((long)y0 * p.W + x0) * p.Cin));
       h8 b = __builtin_bit_cast(h8, ldg16(base + ((long)y0 * p.W + x1) * p.Cin));
@@ -340,19 +339,10 @@ __device__ __forceinline__ void tile_coords(int bid, int nwg, int tiles_m, int t
   tn = in_group / gsize;
 }
 
-__device__ __forceinline__ void glds16(const void* src, h16* lds_base) {
-  __builtin_amdgcn_global_load_lds(src, (VDA_LDS void*)lds_base, 16, 0, 0);
-}
-
 template <int KB>
 __device__ __forceinline__ int swzk(int row, int chunk) {  // half offset in a [rows][KB] tile
   constexpr int CH = KB / 8;
   return row * KB + ((chunk ^ ((row >> 1) & (CH - 1))) << 3);
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
 // NS-stage LDS-DMA pipeline: tile kt+NS-1 is issued while tile kt is multiplied; before reading a

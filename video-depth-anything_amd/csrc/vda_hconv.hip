@@ -31,6 +31,7 @@
 // stride leaves the ds_read_b128 lane groups 2-way conflicted at worst (10 slots would be conflict-free
 // but do not fit the LDS).
 #include "vda_internal.h"
+#include "vda_halo.h"
 #include <type_traits>
 
 namespace {
@@ -42,7 +43,7 @@ constexpr int HC_PSTR = 9;                           // 16-B slots per patch pix
 constexpr int HC_PP = (HC_NPIX * HC_PSTR + 63) / 64; // 48 one-KiB DMA pieces per 64-channel slab
 constexpr int HC_PSLOT = HC_PP * 512;                // halfs per patch slot
 constexpr int HC_PPW = (HC_PP + 7) / 8;              // patch pieces per wave: every wave owns exactly 6
-static_assert(HC_PP % 8 == 0, "the hc_wait counts assume every wave issues HC_PPW patch pieces");
+static_assert(HC_PP % 8 == 0, "the wait_vmcnt counts assume every wave issues HC_PPW patch pieces");
 constexpr int HC_BK = 64;
 constexpr int HC_HALF = 128 * HC_BK;                 // halfs per 128-row W region
 constexpr int HC_WBUF = 2 * HC_HALF;                 // one K step of W (256 rows)
@@ -59,11 +60,6 @@ __device__ unsigned long long g_hts[8192][6];
 #endif
 
 __device__ __forceinline__ int hc_swz(int row, int chunk) { return row * HC_BK + ((chunk ^ ((row >> 1) & 7)) << 3); }
-
-template <int N>
-__device__ __forceinline__ void hc_wait() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 struct HconvArgs {
   const h16* x;     // [BT, H, W, Cin]
@@ -135,7 +131,7 @@ __global__ __launch_bounds__(512) void hconv256_kernel(HconvArgs a) {
     const int q = wave + 8 * j;
     if (q < HC_PP) {
       const void* src = poff[j] >= 0 ? (const void*)(xf0 + poff[j] + slab * 64) : zero;
-      __builtin_amdgcn_global_load_lds(src, (VDA_LDS void*)(psm + (slab & 1) * HC_PSLOT + q * 512), 16, 0, 0);
+      glds16(src, psm + (slab & 1) * HC_PSLOT + q * 512);
     }
   };
 
@@ -183,9 +179,9 @@ __global__ __launch_bounds__(512) void hconv256_kernel(HconvArgs a) {
   stage_w(0, 0, 1);
   if (NK > 1) {
     stage_w(1, 1, 1);
-    hc_wait<2>();
+    wait_vmcnt<2>();
   } else {
-    hc_wait<0>();
+    wait_vmcnt<0>();
   }
   __builtin_amdgcn_s_barrier();
   // PRE (the RCU's relu(x) input): the patch is rectified once in LDS after it lands (2 passes per
@@ -283,9 +279,9 @@ __global__ __launch_bounds__(512) void hconv256_kernel(HconvArgs a) {
       load_w(base, 0);
       if (more2) {
         stage_w(kt + 2, cb, 1);
-        hc_wait<2>();
+        wait_vmcnt<2>();
       } else {
-        hc_wait<0>();
+        wait_vmcnt<0>();
       }
       mma(1, 0);
     };
@@ -326,15 +322,12 @@ __global__ __launch_bounds__(512) void hconv256_kernel(HconvArgs a) {
   const __amdgpu_buffer_rsrc_t rs2 = __builtin_amdgcn_make_buffer_rsrc(
       (void*)((up2 ? a.res2 : a.y) + (up2 ? (long)bt * a.r2h * a.r2w * 256 : fbase)), (short)0,
       up2 ? (int)((long)a.r2h * a.r2w * 512) : (int)fbytes, 0x00020000);
-  const float usy = a.r2h > 0 && H > 1 ? (float)(a.r2h - 1) / (float)(H - 1) : 0.f;
-  const float usx = a.r2w > 0 && W > 1 ? (float)(a.r2w - 1) / (float)(W - 1) : 0.f;
+  const float usy = a.r2h > 0 ? ac_scale(a.r2h, H) : 0.f, usx = a.r2w > 0 ? ac_scale(a.r2w, W) : 0.f;
   auto up_load = [&](int it, h8* t4, float& wx, float& wy) {
     const int yy = min(y0 + (it >> 1), H - 1), xx = min(x0 + row0 + 16 * (it & 1), W - 1);
-    const float fy = usy * (float)yy, fx = usx * (float)xx;
-    const int sy0 = (int)fy, sx0 = (int)fx;
-    const int sy1 = min(sy0 + 1, a.r2h - 1), sx1 = min(sx0 + 1, a.r2w - 1);
-    wy = ac_weight(usy, (float)yy, sy0);
-    wx = ac_weight(usx, (float)xx, sx0);
+    int sy0, sy1, sx0, sx1;
+    ac_coord(yy, a.r2h, usy, sy0, sy1, wy);
+    ac_coord(xx, a.r2w, usx, sx0, sx1, wx);
     const unsigned r0 = (unsigned)(sy0 * a.r2w), r1 = (unsigned)(sy1 * a.r2w), c8 = (unsigned)q * 16u;
     t4[0] = __builtin_bit_cast(h8, __builtin_amdgcn_raw_buffer_load_b128(rs2, (r0 + sx0) * 512u + c8, 0, 0));
     t4[1] = __builtin_bit_cast(h8, __builtin_amdgcn_raw_buffer_load_b128(rs2, (r0 + sx1) * 512u + c8, 0, 0));

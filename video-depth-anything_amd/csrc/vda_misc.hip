@@ -1,5 +1,6 @@
 // Bilinear resize, patch-embed im2col, and the C-ABI error plumbing.
 #include "vda_internal.h"
+#include "vda_halo.h"
 #include <cstdio>
 #include <cstring>
 
@@ -33,15 +34,6 @@ extern "C" const char* vda_last_error(void) { return g_err; }
 
 namespace {
 
-// align_corners=True source coordinate (torch area_pixel_compute_source_index for bilinear)
-__device__ __forceinline__ void ac_coord(int o, int in, int out, int& i0, int& i1, float& w) {
-  const float sc = out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f;
-  const float f = sc * (float)o;
-  i0 = (int)f;
-  i1 = min(i0 + 1, in - 1);
-  w = ac_weight(sc, (float)o, i0);
-}
-
 // One block row per PAIR of output rows (bt, oy), (bt, oy + 1): the two source rows and the y weight
 // are fixed per row, and the (ox, 8-channel chunk) index within a row needs only 32-bit math.  When
 // both rows blend the same two source rows (every upscale by >= 2 pairs them), the second row reuses
@@ -53,15 +45,15 @@ __global__ __launch_bounds__(256) void upsample_kernel(const h16* __restrict__ x
                                                        int H, int W, int C, int Ho, int Wo) {
   const unsigned nch = (unsigned)C >> 3;
   const unsigned row_items = (unsigned)Wo * nch;
-  const float sx = Wo > 1 ? (float)(W - 1) / (float)(Wo - 1) : 0.f;
+  const float sy = ac_scale(H, Ho), sx = ac_scale(W, Wo);
   for (int r = 2 * blockIdx.y; r < rows; r += 2 * gridDim.y) {
     const int bt = r / Ho, oy = r - bt * Ho;
     int y0, y1; float wy;
-    ac_coord(oy, H, Ho, y0, y1, wy);
+    ac_coord(oy, H, sy, y0, y1, wy);
     const bool two = r + 1 < rows;
     const int btB = (r + 1) / Ho, oyB = r + 1 - btB * Ho;
     int y0B, y1B; float wyB;
-    ac_coord(oyB, H, Ho, y0B, y1B, wyB);
+    ac_coord(oyB, H, sy, y0B, y1B, wyB);
     const bool share = btB == bt && y0B == y0 && y1B == y1;
     const h16* r0 = x + ((long)bt * H + y0) * W * C;
     const h16* r1 = x + ((long)bt * H + y1) * W * C;
@@ -78,9 +70,8 @@ __global__ __launch_bounds__(256) void upsample_kernel(const h16* __restrict__ x
       for (int u = 0; u < UP; ++u) {
         const unsigned i = min(i0 + u * 256u, row_items - 1);
         const unsigned ox = i / nch, ch = i - ox * nch;
-        const float f = sx * (float)ox;
-        const int x0 = (int)f, x1 = min(x0 + 1, W - 1);
-        wx[u] = ac_weight(sx, (float)ox, x0);  // one explicit fma, as at every fused-resize site
+        int x0, x1;
+        ac_coord((int)ox, W, sx, x0, x1, wx[u]);
         o0[u] = (unsigned)x0 * C + ch * 8;
         o1[u] = (unsigned)x1 * C + ch * 8;
         a[u] = __builtin_bit_cast(h8, ldg16(r0 + o0[u]));

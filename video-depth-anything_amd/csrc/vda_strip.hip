@@ -22,6 +22,7 @@
 // stores; strip_finish_kernel adds the slices in a fixed order (deterministic) and applies the
 // epilogue.  The host picks the split count from a rounds x steps cost model (vda_conv_strip).
 #include "vda_internal.h"
+#include "vda_halo.h"
 
 namespace {
 
@@ -54,13 +55,6 @@ struct StripParams {
   int nsplit, nsl;  // channel-slab splits per tile, slabs per split
 };
 
-__device__ __forceinline__ void st_glds16(const void* src, h16* lds_base) {
-  __builtin_amdgcn_global_load_lds(src, (VDA_LDS void*)lds_base, 16, 0, 0);
-}
-template <int N>
-__device__ __forceinline__ void st_wait() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 __device__ __forceinline__ int st_ppos(int pp, int cd) { return cd ^ ((pp >> 1) & 3); }
 __device__ __forceinline__ int st_wpos(int n, int cd) { return cd ^ ((n >> 1) & 3); }
 
@@ -110,7 +104,7 @@ __global__ __launch_bounds__(512) void strip_conv_kernel(StripParams p) {
     const void* src = zero;
     if (pp < npix && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W)
       src = p.x + (((long)bt * H + iy) * W + ix) * p.Cin + slab * ST_SLAB + cd * 8;
-    st_glds16(src, patch + (u & 1) * ST_PBUF + q * 512);
+    glds16(src, patch + (u & 1) * ST_PBUF + q * 512);
   };
   auto dma_w = [&](int gs) {
     const int u = gs / 9, tap = gs - u * 9;
@@ -121,7 +115,7 @@ __global__ __launch_bounds__(512) void strip_conv_kernel(StripParams p) {
       const int s = piece * 64 + lane;
       const int n = s / ST_CPX, pos = s - n * ST_CPX;
       const int cd = st_wpos(n, pos);
-      st_glds16(p.w + (long)n * K + tap * p.Cin + slab * ST_SLAB + cd * 8, wbuf + (gs % ST_WR) * ST_WBUF + piece * 512);
+      glds16(p.w + (long)n * K + tap * p.Cin + slab * ST_SLAB + cd * 8, wbuf + (gs % ST_WR) * ST_WBUF + piece * 512);
     }
   };
 
@@ -129,9 +123,9 @@ __global__ __launch_bounds__(512) void strip_conv_kernel(StripParams p) {
   dma_w(0);
   if (ST_WR == 3 && my_steps > 1) {
     dma_w(1);
-    st_wait<2>();
+    wait_vmcnt<2>();
   } else {
-    st_wait<0>();
+    wait_vmcnt<0>();
   }
   __builtin_amdgcn_s_barrier();
 
@@ -238,11 +232,11 @@ __global__ __launch_bounds__(512) void strip_conv_kernel(StripParams p) {
       // (tap 1: before this step's weights; they then land by the end of tap 1, 8 steps early)
       const bool p_prev = tap == 1 && u + 1 < my_units;
       if (issue_w) {
-        if (issue_p || p_prev) st_wait<ST_PPW + 2>();
-        else st_wait<2>();
+        if (issue_p || p_prev) wait_vmcnt<ST_PPW + 2>();
+        else wait_vmcnt<2>();
       } else {
-        if (issue_p || p_prev) st_wait<ST_PPW>();
-        else st_wait<0>();
+        if (issue_p || p_prev) wait_vmcnt<ST_PPW>();
+        else wait_vmcnt<0>();
       }
     }
     __builtin_amdgcn_s_barrier();
