@@ -14,15 +14,11 @@ extern "C" {
 
 /* GEMM / conv tile configuration (-1 = automatic; 0 = 128x128/4 waves, 1 = 256x128/8 waves,
  * 2 = 128x64/4 waves, 3 = 256x256/8 waves; -2 / -3 = automatic tiles with the strip-tiled 3x3 conv for
- * no / every Cout = 256 shape; 9 = depth tail on a materialised resize instead of the resize fused into
- * the halo conv; 10 + cfg = implicit-GEMM depth tail). */
+ * no / every Cout = 256 shape; 10 + cfg = implicit-GEMM depth tail, which ignores the values below 10). */
 int vda_debug_force_tile(int32_t cfg);
 /* Phased 256-row GEMM: persist_blocks > 0 launches that many persistent blocks (0 = one block per tile,
  * -1 = automatic: one per CU). */
 int vda_debug_gemm_sched(int32_t persist_blocks);
-/* 1: the residual + row-statistics GEMMs (proj / fc2) through the register epilogue (bit-identical;
- * measured slower than the staged epilogue the product uses); 0 = staged. */
-int vda_debug_gemm_epi(int32_t res_register);
 /* Strip-tiled 3x3 conv: split every tile's input channels over nsplit work items (1, 2, 4, 8; must divide
  * Cin / 32); 0 = automatic. */
 int vda_debug_strip_split(int32_t nsplit);
@@ -30,7 +26,8 @@ int vda_debug_strip_split(int32_t nsplit);
  * 1 = every shape it serves. */
 int vda_debug_hconv(int32_t mode);
 /* Depth tail: -1 = automatic (the 2-blocks-per-CU depth conv with the resize fused), 2 = the same conv on
- * a materialised resize (bit-identical; needs the workspace), 0 = the older 8-wave halo kernels. */
+ * a materialised resize (bit-identical; needs the workspace).  Any other value is refused (non-zero return,
+ * knob unchanged). */
 int vda_debug_dconv(int32_t mode);
 /* Attention kernels: spatial 1 = the round-1 16x16x32 kernel; temporal 1 = the direct-load kernel. */
 int vda_debug_attn(int32_t spatial_old, int32_t temporal_old);

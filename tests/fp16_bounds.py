@@ -87,9 +87,9 @@ def gemm_ref_bound(x, w, *, bias=None, rowbias=None, rdiv=1, rmod=1, gamma=None,
 
     staged=False, the one-tile-per-block kernels (vda_gemm_tile.h epi_store4 / epi_geglu4): the accumulator and
     the whole epilogue including the residual adds are fp32 and the store is the ONLY fp16 rounding: no v_i.
-    staged=True, the phased kernels (vda_gemm_phased.h: the LDS-staged epilogue's phase 1 / phase 2 and the
-    register epilogue EK 2): t = gamma * act(...) is rounded to fp16, then res and res2 are added as packed
-    fp16 vectors, one rounding per add, so t and (with both residuals) t + res are intermediates v_i.
+    staged=True, the phased kernels (vda_gemm_phased.h: the LDS-staged epilogue's phase 1 / phase 2): t = gamma *
+    act(...) is rounded to fp16, then res and res2 are added as packed fp16 vectors, one rounding per add, so t
+    and (with both residuals) t + res are intermediates v_i.
     phi_table=True: GELU / GEGLU through the Phi table of the phased 256x256 kernels (gelu_err).
 
     ln: the LayerNorm fold, bounded for the folded form the kernel evaluates, rstd * (sum x w' - mean * colsum) +
@@ -1118,7 +1118,7 @@ def conv_im2col_ref(x, ks, stride, pad):
 
 
 # =====================================================================================================
-# Depth tail (csrc/vda_depth_head.hip -> vda_dconv.hip / vda_depth.hip / the implicit-GEMM depth kernel)
+# Depth tail (csrc/vda_depth_head.hip -> vda_dconv.hip / the implicit-GEMM depth kernel)
 # =====================================================================================================
 def split_hi_lo(w1):
     """The fp32 3x3 weights [32, C, 3, 3] as the fp16 pair the kernels multiply: hi = fp16(w), lo = fp16(w - hi)."""
@@ -1131,8 +1131,8 @@ def depth_head_ref_bound(x, w1, b1, w2, b2, Ho, Wo):
     values), w1 [32, C, 3, 3] fp32, w2 [32] -> (ref, bound) [BT, Ho, Wo], fp32 output (no fp16 store).
 
     Reference: float64 resize, rounded to fp16, then the conv with the weights hi + lo the kernels really
-    multiply (split_hi_lo), everything else float64.  Kernel (vda_dconv.hip:1-11, :392-396; the halo kernels of
-    vda_depth.hip and the implicit-GEMM depth tail keep the same terms): 64 MFMA rows, hi and lo accumulated
+    multiply (split_hi_lo), everything else float64.  Kernel (vda_dconv.hip:1-11, :392-396; the
+    implicit-GEMM depth tail keeps the same terms): 64 MFMA rows, hi and lo accumulated
     separately in fp32 over K = 9 C products each, h_j = relu(acc_hi + acc_lo + b1): gamma(K + 3) of the absolute
     image; then 4 products per lane, two lane-group shuffles and b2: gamma(32 + 2) of sum |w2 h| + |b2|.
     The resized map: the kernels blend in fp32 (bilerp8, _resize_err) and round to fp16, so an element whose

@@ -306,11 +306,10 @@ def test_gemm_phased_ln_fold(kind, N):
     note(f"gemm phased {kind} N={N}", worst)
 
 
-@pytest.mark.parametrize("epi_knob", [0, 1])
 @pytest.mark.parametrize("N", [256, 512])
-def test_gemm_phased_res_stats_out(N, epi_knob):
-    """res + stats_out through the staged epilogue and (gemm_epi = 1) the register epilogue EK 2, M = 4097: the
-    output under the per-element bound, and the [M, N / 256, 2] partial (sum, sum of squares) of the STORED
+def test_gemm_phased_res_stats_out(N):
+    """res + stats_out through the staged epilogue, M = 4097: the output under the per-element bound, and the
+    [M, N / 256, 2] partial (sum, sum of squares) of the STORED
     fp16 row against float64 sums of the kernel's own output per 256-column part (fp32 accumulation of 256
     terms: fp16_bounds.row_stats_ref_bound), with a NaN spare row after row M - 1 that must stay NaN.  Output
     and statistics are bit-identical to cfg 4 forced (the in-epilogue statistics, not the separate pass)."""
@@ -323,17 +322,16 @@ def test_gemm_phased_res_stats_out(N, epi_knob):
     buf, out = framed2d(M, N)
     res = h(c["kw"]["res"])
     stats = torch.full((M + 1, parts, 2), float("nan"), device=DEV, dtype=torch.float32)
-    with T.route(gemm_epi=epi_knob, gemm_sched=3):
+    with T.route(gemm_sched=3):
         T.gemm_kw(h(c["x"]), h(c["w"]), out, bias=f32(c["kw"]["bias"]), res=res, stats_out=stats)
-    worst = assert_elementwise(out, ref, bound, f"gemm res+stats N={N} epi {epi_knob}")
+    worst = assert_elementwise(out, ref, bound, f"gemm res+stats N={N}")
     assert rel(out, ref) < BAR_GEMM and frame2d_ok(buf, M, N)
     buf2, out2 = framed2d(M, N)
     stats2 = torch.full_like(stats, float("nan"))
-    forced(T, 4, gemm_epi=epi_knob, gemm_sched=3)(h(c["x"]), h(c["w"]), out2,
-                                                  dict(bias=f32(c["kw"]["bias"]), res=res, stats_out=stats2))
+    forced(T, 4, gemm_sched=3)(h(c["x"]), h(c["w"]), out2, dict(bias=f32(c["kw"]["bias"]), res=res, stats_out=stats2))
     assert torch.equal(out, out2) and torch.equal(stats[:M], stats2[:M]), "the automatic route is not the phased kernel"
-    ws = check_stats(stats, out, M, parts, f"stats_out N={N} epi {epi_knob}")
-    note(f"gemm phased res+stats N={N} gemm_epi={epi_knob} (stats {ws:.3f})", worst)
+    ws = check_stats(stats, out, M, parts, f"stats_out N={N}")
+    note(f"gemm phased res+stats N={N} (stats {ws:.3f})", worst)
 
 
 # =====================================================================================================
@@ -456,7 +454,7 @@ def bias_case(BT, Cin, Cout, H, W, relu, seed, up=None):
 
 @pytest.mark.parametrize("H,W,relu", [(129, 128, False), (143, 115, True)])
 def test_halo_cout128_product_route(H, W, relu):
-    """The 128-output halo conv (vda_depth.hip, 16 x 16 tiles) on the automatic route (H * W >= 128^2): one
+    """The 128-output halo conv (vda_oc1.hip, 16 x 16 tiles) on the automatic route (H * W >= 128^2): one
     row more than 8 whole tiles, and ragged tiles both ways.  Bias [+ ReLU], one rounding."""
     _, worst = run_conv(bias_case(1, 64, 128, H, W, relu, H), {}, False, f"halo128 {H}x{W}", product=True)
     note(f"halo Cout 128 {H}x{W}", worst)

@@ -476,14 +476,19 @@ def staging_case(C, Hs, Ws, BT):
     return (x, w1, b1, w2, b2), h(x.permute(0, 2, 3, 1)), args
 
 
+# C = 32 keeps the ids it had before C = 64 joined it
+STAGING_C = [pytest.param(C, *case, id=("" if C == 32 else f"C{C}-") + "-".join(str(v) for v in case))
+             for C in (32, 64) for case in STAGING_CASES]
+
+
 @pytest.mark.parametrize("BT", [1, 2])
-@pytest.mark.parametrize("Hs,Ws,served", STAGING_CASES)
-def test_depth_head_staging_boundary(Hs, Ws, served, BT):
+@pytest.mark.parametrize("C,Hs,Ws,served", STAGING_C)
+def test_depth_head_staging_boundary(C, Hs, Ws, served, BT):
     """Both sides of the one predicate (halo_fused_fits) that decides whether the depth conv builds its patches
-    from a staged source window, and with it the depth head's workspace: C = 32, no workspace where served and
-    the resized map where declined; the output within the bound, bit for bit the materialised resize + the same
-    conv (tuning build, dconv = 2), and nothing stored outside it."""
-    C, S = 32, STAGING_OUT
+    from a staged source window, and with it the depth head's workspace: C = 32 and 64 (one and two 32-channel
+    slabs), no workspace where served and the resized map where declined; the output within the bound, bit for
+    bit the materialised resize + the same conv (tuning build, dconv = 2), and nothing stored outside it."""
+    S = STAGING_OUT
     case, xh, args = staging_case(C, Hs, Ws, BT)
     ref, bound = fb.depth_head_ref_bound(*case, S, S)
     what = f"depth tail staging C={C} {Hs}x{Ws}->{S}x{S} BT={BT}"
@@ -497,25 +502,6 @@ def test_depth_head_staging_boundary(Hs, Ws, served, BT):
     assert torch.equal(y, y2), f"{what}: differs from resize + conv"
     assert guard_ok(buf2)
     note(what, worst)
-
-
-@pytest.mark.parametrize("BT", [1, 2])
-@pytest.mark.parametrize("Hs,Ws,served", STAGING_CASES)
-def test_depth_head_staging_boundary_halo(Hs, Ws, served, BT):
-    """The same boundary on the 8-wave halo route (tuning build, dconv = 0) at C = 64: its workspace, and the
-    fused output bit for bit the materialised one (force_tile = 9)."""
-    C, S = 64, STAGING_OUT
-    _, xh, args = staging_case(C, Hs, Ws, BT)
-    what = f"depth tail staging (halo) C={C} {Hs}x{Ws}->{S}x{S} BT={BT}"
-    T = tune_lib()
-    with T.route(dconv=0):
-        assert T.depth_head_workspace(BT, Hs, Ws, C, S, S) == (0 if served else BT * S * S * C * 2), what
-        buf, y = c_depth_head(T.lib, xh, *args)
-        with T.route(force_tile=9):
-            assert T.depth_head_workspace(BT, Hs, Ws, C, S, S) == BT * S * S * C * 2
-            buf2, y2 = c_depth_head(T.lib, xh, *args)
-    assert torch.equal(y, y2), f"{what}: differs from resize + conv"
-    assert guard_ok(buf) and guard_ok(buf2), f"{what}: a store outside the output"
 
 
 @pytest.mark.parametrize("C,Hin,Win,Ho,Wo", [(64, 8, 20, 33, 47), (64, 37, 37, 19, 19), (40, 9, 9, 15, 17)])

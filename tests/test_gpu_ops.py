@@ -398,8 +398,8 @@ def test_patch_embed_im2col_gemm():
 @pytest.mark.parametrize("C,Hin,Win,Ho,Wo,BT", [(32, 16, 20, 28, 42, 2), (128, 20, 24, 37, 51, 2), (64, 9, 9, 16, 16, 1),
                                                  (128, 37, 37, 70, 70, 3), (96, 10, 12, 20, 22, 1)])
 def test_depth_head_fp32(C, Hin, Win, Ho, Wo, BT):
-    """Depth tail: the halo-tiled kernel (C = 32 or C % 64 == 0; tile edges 16 with partial tiles here),
-    the implicit-GEMM kernel (other C, and the tuning override) vs torch fp32."""
+    """Depth tail: the depth conv (C % 32 == 0; tile edges 16 with partial tiles here) and the implicit-GEMM
+    kernel (the tuning override) vs torch fp32."""
     x = rnd(BT, C, Hin, Win, seed=45)
     b1 = rnd(32, scale=0.1, seed=47)
     w2, b2 = rnd(1, 32, 1, 1, seed=48).abs() * 0.2, torch.tensor([0.05])
@@ -626,9 +626,7 @@ def test_conv3x3_strip_split(Cin, H, W, BT, mode, split):
                                                  (64, 30, 17, 53, 31, 2), (128, 12, 12, 12, 12, 1), (64, 5, 40, 33, 47, 1)])
 def test_depth_head_fused_resize(C, Hin, Win, Ho, Wo, BT):
     """Depth tail with the bilinear resize fused into the patch building of the depth conv (default):
-    bit-identical to the materialised resize + the same conv (tuning build: vda_debug_dconv(2)); and the
-    older fused 8-wave halo conv (vda_debug_dconv(0)) bit-identical to the materialised resize + halo conv
-    (vda_debug_force_tile(9)),
+    bit-identical to the materialised resize + the same conv (tuning build: vda_debug_dconv(2)),
     both interpolating with the same fp32 formula and fp16 rounding; partial tiles, non-square maps,
     identity-size resize, aspect ratios far from 1."""
     x = rnd(BT, C, Hin, Win, seed=145)
@@ -646,12 +644,6 @@ def test_depth_head_fused_resize(C, Hin, Win, Ho, Wo, BT):
     with T.route(dconv=2):  # the same conv on a materialised resize
         y_mat2 = T.depth_head(xh, *args)
     assert torch.equal(y, y_mat2)
-    with T.route(dconv=0):
-        y_fused = T.depth_head(xh, *args)
-    with T.route(force_tile=9):
-        y_mat = T.depth_head(xh, *args)
-    assert torch.equal(y_fused, y_mat)  # the older 8-wave halo kernels, fused vs materialised
-    assert rel(y_fused, ref) < 1e-5
     assert rel(y, ref) < 1e-5
 
 
@@ -920,16 +912,6 @@ def test_gemm_epilogue_row_stats(M, N, K):
     yb = ops.gemm(tok, wg.to(DEV), bias=bb, ln_stats=ops.row_stats(tok, 1e-6), ln_colsum=c1)
     ref = F.linear(F.layer_norm(y, (N,), gam, bet, eps=1e-6), w2)
     assert rel(ya, ref) < 2e-3 and rel(ya, yb) < 1e-3
-    # the register residual epilogue of the tuning build (vda_debug_gemm_epi(1), EK 2 for the phased
-    # shapes): bit-identical outputs; the statistics sum in another order
-    tok2, st2 = r.to(DEV).contiguous(), torch.full((M + 1, P, 2), float("nan"), device=DEV)
-    xh, wh, bf = h(x), h(w), f32(b)
-    e = Epilogue(rdiv=1, rmod=1, bias=bf.data_ptr(), res=tok2.data_ptr(), ldres=N, stats_out=st2.data_ptr())
-    with tune_lib().route(gemm_epi=1) as T:
-        T.gemm(xh, wh, tok2, e, M, N, K)
-    torch.cuda.synchronize()
-    assert torch.equal(tok2, tok)
-    assert torch.allclose(st2[:M], st[:M], rtol=1e-5, atol=1e-4)
 
 
 @pytest.mark.parametrize("M,P,rowbias,nobias", [(4097, 3, False, False), (4097, 1, False, False), (4097, 0, False, False),

@@ -34,7 +34,7 @@ def _attn_scale(D):
 
 
 class TuneLib:
-    DEFAULTS = dict(force_tile=-1, strip_split=0, hconv=-1, dconv=-1, gemm_epi=0, attn=(0, 0), gemm_sched=-1)
+    DEFAULTS = dict(force_tile=-1, strip_split=0, hconv=-1, dconv=-1, attn=(0, 0), gemm_sched=-1)
 
     def __init__(self, path):
         self.lib = ctypes.CDLL(path)

@@ -7,7 +7,7 @@ FL="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wno-unused-result -I include -mu
 for spec in "$@"; do
   name=${spec%%:*}; defs=${spec#*:}
   D=build/var/$name; mkdir -p $D
-  S=${SRC:-vda_depth}
+  S=${SRC:-vda_oc1}
   /opt/rocm/bin/hipcc $FL $defs $EXTRA -c video-depth-anything_amd/csrc/$S.hip -o $D/$S.o
   objs=$(ls build/*.o | grep -v "/$S.o" | grep -v "/vda_torch.o")
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $objs $D/$S.o -o $D/libvda.so

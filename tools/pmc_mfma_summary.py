@@ -31,7 +31,7 @@ TAGS = [
     (r"spatial_attn32_kernel", "spatial_attention"),
     (r"temporal_attn_lds_kernel", "temporal_attention"),
     (r"depth_conv_kernel", "depth_conv"),
-    (r"halo_conv_kernel<64, 128, 1|halo_conv_kernelILi64ELi128ELi1E", "output_conv1"),
+    (r"halo_conv_kernel", "output_conv1"),
     (r"^hconv256_kernel", "conv3x3_halo256"),
     (r"^strip_conv", "conv3x3_strip"),
 ]

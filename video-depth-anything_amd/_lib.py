@@ -34,8 +34,8 @@ EXPORTED = (
     "vda_temporal_attention_f32", "vda_upsample_bilinear_f32", "vda_patch_im2col_f32", "vda_depth_head_f32",
 )
 # The tuning build (make tune -> build/tune/libvda.so, include/vda_tune.h) adds these.
-TUNE_EXPORTED = ("vda_debug_force_tile", "vda_debug_gemm_sched", "vda_debug_gemm_epi",
-                 "vda_debug_strip_split", "vda_debug_hconv", "vda_debug_dconv", "vda_debug_attn")
+TUNE_EXPORTED = ("vda_debug_force_tile", "vda_debug_gemm_sched", "vda_debug_strip_split", "vda_debug_hconv",
+                 "vda_debug_dconv", "vda_debug_attn")
 TUNE_LIB_PATH = os.path.join(os.path.dirname(_HERE), "build", "tune", "libvda.so")
 
 ACT_NONE, ACT_GELU, ACT_GEGLU, ACT_RELU = 0, 1, 2, 3
@@ -122,7 +122,6 @@ def _declare(lib):
         "vda_debug_strip_split": ([I], I),
         "vda_debug_hconv": ([I], I),
         "vda_debug_dconv": ([I], I),
-        "vda_debug_gemm_epi": ([I], I),
         "vda_debug_attn": ([I, I], I),
     }
     for name, (args, res) in sig.items():

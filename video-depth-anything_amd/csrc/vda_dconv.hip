@@ -7,7 +7,7 @@
 // Shape of the work: N = 64 MFMA rows only, so the LDS bytes per MFMA are set by how many pixels
 // each wave multiplies against the whole 64-row W.  Here a wave owns 64 pixels (4 rows of a 16 x 16
 // output tile) x all 64 rows: per tap and 32-channel slab 4 X + 4 W ds_read_b128 feed 16 MFMAs (the
-// 8-wave halo kernel of vda_depth.hip reads 6 per 8).  Every lane ends up with hi and lo of the same
+// 8-wave halo tail this kernel replaced read 6 per 8).  Every lane ends up with hi and lo of the same
 // 4 channels, so the hi + lo + b1, ReLU and the 32 -> 1 dot are wave-local (two lane-group shuffles).
 //
 // Blocks of 4 waves (one per SIMD), TWO blocks per CU (78 KiB LDS each): the blocks do not share
@@ -381,10 +381,10 @@ extern "C" int vda_debug_dconv_timestamps(void* host) {
 }
 #endif
 
-// vda_debug_dconv (tuning build): -1 automatic (fused), 0 never, 2 resize + unfused depth conv
+// vda_debug_dconv (tuning build): -1 automatic (fused), 2 resize + unfused depth conv
 VDA_KNOB(int, g_dconv_mode, -1);
 
-bool vda_depth_conv_serves(int H, int W, int C) { return C % 32 == 0 && C > 0 && H > 0 && W > 0 && g_dconv_mode != 0; }
+bool vda_depth_conv_serves(int H, int W, int C) { return C % 32 == 0 && C > 0 && H > 0 && W > 0; }
 
 // depth tail on the already-resized map U [BT, H, W, C] (C % 32 == 0).  Returns 1 when not served.
 int vda_depth_conv(const void* U, const void* w1, const float* b1, const float* w2, const float* b2, float* depth,
@@ -421,6 +421,7 @@ int vda_depth_conv_fused(const void* x, const void* w1, const float* b1, const f
 
 #ifdef VDA_TUNING
 extern "C" int vda_debug_dconv(int32_t mode) {
+  if (mode != -1 && mode != 2) return 1;
   g_dconv_mode = mode;
   return 0;
 }

@@ -1,6 +1,6 @@
 // Depth-head router: the DPT head's tail (bilinear resize to (Ho, Wo), 3x3 conv C -> 32, ReLU, 1x1 conv
-// 32 -> 1, ReLU; fp32 depth) through the depth conv of vda_dconv.hip, the halo kernels of vda_depth.hip
-// or the implicit-GEMM tail of vda_gemm.hip.  Host code only.
+// 32 -> 1, ReLU; fp32 depth) through the depth conv of vda_dconv.hip or, for the channel counts it does
+// not serve, the implicit-GEMM tail of vda_gemm.hip.  Host code only.
 #include "vda_internal.h"
 
 extern "C" int vda_depth_head(const void* x, const void* w1, const float* b1, const float* w2, const float* b2,
@@ -11,38 +11,26 @@ extern "C" int vda_depth_head(const void* x, const void* w1, const float* b1, co
   VDA_CHECK_ARG(C % 8 == 0, "depth head needs C % 8 == 0");
   hipStream_t st = (hipStream_t)stream;
   int rc;
-  // default: the depth conv of vda_dconv.hip (two 4-wave blocks per CU, 64 pixels x all 64 hi/lo rows
-  // per wave) with the bilinear resize fused into its patch building (the resized map is never
-  // written); vda_debug_dconv(2): bilinear resize into ws + the same conv on the materialised map
-  // (bit-identical); vda_debug_dconv(0): the older 8-wave halo kernels below.
-  if (g_force_tile == -1) {
+  // vda_debug_force_tile(10 + cfg) (tuning build): the implicit-GEMM tail in tile configuration cfg for
+  // every shape; lower values are the GEMM's and the conv's and do not move the depth tail
+  const bool gemm_tail = g_force_tile >= 10;
+  // 1) the depth conv of vda_dconv.hip (two 4-wave blocks per CU, 64 pixels x all 64 hi/lo rows per wave)
+  //    with the bilinear resize fused into its patch building: the resized map is never written
+  if (!gemm_tail) {
     rc = vda_depth_conv_fused(x, w1, b1, w2, b2, depth, BT, Hin, Win, Ho, Wo, C, st);
     if (rc != 1) return rc;
   }
-  if (g_force_tile == -1 && vda_depth_conv_serves(Ho, Wo, C)) {
-    VDA_CHECK_ARG(ws, "depth head: needs the resize workspace (vda_depth_head_workspace)");
-    rc = vda_upsample_bilinear(x, ws, BT, Hin, Win, C, Ho, Wo, stream);
-    if (rc) return rc;
+  // 2) bilinear (align_corners=True) resize of the output_conv1 map into ws, fp16 like the reference's
+  //    autocast interpolate (dpt_temporal.py:92-94), and the same conv on the materialised map
+  //    (bit-identical to 1; also vda_debug_dconv(2))
+  VDA_CHECK_ARG(ws, "depth head: needs the resize workspace (vda_depth_head_workspace)");
+  rc = vda_upsample_bilinear(x, ws, BT, Hin, Win, C, Ho, Wo, stream);
+  if (rc) return rc;
+  if (!gemm_tail) {
     rc = vda_depth_conv(ws, w1, b1, w2, b2, depth, BT, Ho, Wo, C, st);
     if (rc != 1) return rc;
   }
-  // 0) resize fused into the halo conv's patch staging (the resized map is never written;
-  //    bit-identical to 1 + 2).  vda_debug_force_tile(9) takes the materialised path below.
-  if (g_force_tile < 9) {
-    rc = vda_depth_halo_fused(x, w1, b1, w2, b2, depth, BT, Hin, Win, Ho, Wo, C, st);
-    if (rc != 1) return rc;
-  }
-  VDA_CHECK_ARG(ws, "depth head: this shape needs the resize workspace (vda_depth_head_workspace)");
-  // 1) bilinear (align_corners=True) resize of the output_conv1 map to (Ho, Wo), fp16 like the
-  //    reference's autocast interpolate (dpt_temporal.py:92-94)
-  rc = vda_upsample_bilinear(x, ws, BT, Hin, Win, C, Ho, Wo, stream);
-  if (rc) return rc;
-  // 2) 3x3 conv C -> 32 with split-fp16 weights + fused ReLU / 1x1 / ReLU epilogue: the halo-tiled
-  //    kernel (vda_depth.hip) unless a tuning override asks for the implicit-GEMM one
-  if (g_force_tile < 10) {
-    rc = vda_depth_halo(ws, w1, b1, w2, b2, depth, BT, Ho, Wo, C, st);
-    if (rc != 1) return rc;
-  }
+  // 3) C % 32 != 0: the implicit-GEMM conv with split-fp16 weights + fused ReLU / 1x1 / ReLU epilogue
   GemmParams p{};
   p.x = (const h16*)ws; p.w = (const h16*)w1; p.y = (h16*)depth;
   p.H = Ho; p.W = Wo; p.Cin = C; p.ks = 3; p.stride = 1; p.pad = 1; p.pre_relu = 0;
@@ -55,8 +43,6 @@ extern "C" int vda_depth_head(const void* x, const void* w1, const float* b1, co
 
 extern "C" int64_t vda_depth_head_workspace(int32_t BT, int32_t Hin, int32_t Win, int32_t C, int32_t Ho, int32_t Wo) {
   if (BT <= 0 || Hin <= 0 || Win <= 0 || C <= 0 || Ho <= 0 || Wo <= 0) return 0;
-  if (g_force_tile == -1 && vda_depth_conv_fused_serves(Hin, Win, Ho, Wo, C)) return 0;  // fused: no resized map
-  if (g_force_tile == -1 && vda_depth_conv_serves(Ho, Wo, C)) return (int64_t)BT * Ho * Wo * C * 2;
-  if (g_force_tile < 9 && vda_depth_halo_fused_serves(Hin, Win, Ho, Wo, C)) return 0;  // fused: no resized map
+  if (g_force_tile < 10 && vda_depth_conv_fused_serves(Hin, Win, Ho, Wo, C)) return 0;  // fused: no resized map
   return (int64_t)BT * Ho * Wo * C * 2;
 }

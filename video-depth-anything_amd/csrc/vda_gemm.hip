@@ -20,13 +20,6 @@ VDA_KNOB_DEF(int, g_force_tile, -1);  // vda_debug_force_tile (declared in vda_i
 namespace {
 
 VDA_KNOB(int, g_persist, -1);    // vda_debug_gemm_sched; -1 = automatic
-// vda_debug_gemm_epi: the residual + row-statistics GEMMs (proj / fc2) through the register epilogue
-// (EK 2).  Off: bit-identical but measured slower than the staged epilogue (round 3: proj 94.8 -> 102.9
-// us, fc2 320 -> 334 us; round 4 with whole-line stores / residual loads and asm LDS statistics: proj
-// 104.9 -> 111.9, fc2 319.2 -> 331.2, same box, tools/ab_gemm.py, profiles/r04_ab_gemm_ek2.log): the
-// residual loads issued at the epilogue start are waited for right away, where the staged epilogue
-// covers them with its LDS staging pass.
-VDA_KNOB(int, g_res_epi, 0);
 
 // grid of a phased launch (see gemm256_kernel).  Every block starts at once.  Two start delays were
 // measured and dropped: half of the blocks half a tile late when the last round is short (+0.4 % with
@@ -85,13 +78,6 @@ void launch_phased(const GemmParams& p, hipStream_t st) {
       hipLaunchKernelGGL((gemm256_kernel<XR, WR, CONV, ACT, false, false, 1>), dim3(grid), dim3(512), 0, st, p, tiles_m,
                          tiles_n);
       return;
-    }
-    if constexpr (ACT == VDA_ACT_NONE) {
-      if (g_res_epi && rows1 && e.res && e.stats_out) {
-        hipLaunchKernelGGL((gemm256_kernel<XR, WR, CONV, ACT, false, false, 2>), dim3(grid), dim3(512), 0, st, p, tiles_m,
-                           tiles_n);
-        return;
-      }
     }
   }
   hipLaunchKernelGGL((gemm256_kernel<XR, WR, CONV, ACT, false>), dim3(grid), dim3(512), 0, st, p, tiles_m, tiles_n);
@@ -289,11 +275,6 @@ extern "C" int vda_debug_force_tile(int32_t cfg) {
 
 extern "C" int vda_debug_gemm_sched(int32_t persist_blocks) {
   g_persist = persist_blocks;
-  return 0;
-}
-
-extern "C" int vda_debug_gemm_epi(int32_t res_register) {
-  g_res_epi = res_register;
   return 0;
 }
 #endif

@@ -67,12 +67,6 @@ __device__ __forceinline__ void lds_ld_f4x2(const float* ptr, float4& a, float4&
   asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:16\n\ts_waitcnt lgkmcnt(0)" : "=&v"(a), "=&v"(b)
                : "v"((unsigned)(uintptr_t)(VDA_LDS const float*)ptr) : "memory");
 }
-__device__ __forceinline__ float lds_ld_f1(const float* ptr) {
-  float v;
-  asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v)
-               : "v"((unsigned)(uintptr_t)(VDA_LDS const float*)ptr) : "memory");
-  return v;
-}
 __device__ __forceinline__ void lds_st_f2(float* ptr, float2 v) {
   asm volatile("ds_write_b64 %0, %1" ::"v"((unsigned)(uintptr_t)(VDA_LDS float*)ptr), "v"(v) : "memory");
 }
@@ -211,9 +205,9 @@ constexpr int phased_nit() {
 // tile's prologue wait instead of a full vmcnt(0) at the end of every tile (pre = this tile's
 // prologue was issued that way; vb_next = the tile this block runs next, or -1).
 // EK: compile-time epilogue kind.  0 reads every option of p.epi at run time; 1 = bias (required),
-// no gamma / residual / statistics, row store (qkv, fc1 with their LN fold); 2 = bias + one
-// residual + row statistics, row store (proj, fc2).  The fixed kinds carry no runtime branches on
-// the epilogue, which keeps the uniform state of the persistent loop in SGPRs (no spill reloads,
+// no gamma / residual / statistics, row store (qkv, fc1 with their LN fold); 3 = the same with the LN
+// fold and a per-frame row bias (the motion modules' q/k/v).  The fixed kinds carry no runtime branches
+// on the epilogue, which keeps the uniform state of the persistent loop in SGPRs (no spill reloads,
 // whose vmcnt(0) would drain the chained stores at every tile start).
 template <int XR, int WR, bool CONV, int ACT, bool ROWB, bool LNF, int EK>  // X / W operand regions of 128 rows (BM = 128 XR, BN = 128 WR)
 __device__ __forceinline__ int gemm256_tile(const GemmParams& p, int vb, int tiles_m, int tiles_n, h16* smem,
@@ -231,7 +225,6 @@ __device__ __forceinline__ int gemm256_tile(const GemmParams& p, int vb, int til
   // buffers and the Phi table); colsum takes the prefetched gamma registers (gamma is not allowed).
   static_assert(!(LNF && (ROWB || CONV)), "LNF: dense, no row bias");
   static_assert(EK == 0 || (!CONV && !ROWB), "fixed epilogue kinds: dense, no row bias");
-  static_assert(EK != 2 || (ACT == VDA_ACT_NONE && !LNF), "EK 2: no activation, no LN fold");
   static_assert(EK != 3 || (ACT == VDA_ACT_NONE && LNF), "EK 3: LN fold + per-frame row bias, no activation");
   const bool has_bias = EK ? true : p.epi.bias != nullptr;
   const bool has_gamma = EK ? false : p.epi.gamma != nullptr;
@@ -244,9 +237,9 @@ __device__ __forceinline__ int gemm256_tile(const GemmParams& p, int vb, int til
                        p.epi.store == VDA_STORE_PIXEL_SHUFFLE && p.epi.ps_cout % 256 == 0 && p.epi.ps_win >= 16 &&
                        (long)p.M * p.N * 2 < 0x7fffffffL && (uintptr_t)p.y % 16 == 0;
   const bool rows_store = EK ? true : (p.epi.store == VDA_STORE_ROWS || ps_rows);
-  const bool has_res = EK == 2 ? true : (EK == 1 || EK == 3) ? false : p.epi.res != nullptr;
+  const bool has_res = EK ? false : p.epi.res != nullptr;
   const bool has_res2 = EK ? false : p.epi.res2 != nullptr;
-  const bool has_stats = EK == 2 ? true : (EK == 1 || EK == 3) ? false : p.epi.stats_out != nullptr;
+  const bool has_stats = EK ? false : p.epi.stats_out != nullptr;
   static_assert(XR * WR == 4 && (XR == 2 || XR == 4), "8 waves as XR (m) x 8/XR (n), wave tile 128 x 64");
   constexpr int BM = 128 * XR, BN = 128 * WR;
   constexpr int HALF = 128 * BK;            // halfs per 128-row region (16 KiB)
@@ -738,98 +731,6 @@ __device__ __forceinline__ int gemm256_tile(const GemmParams& p, int vb, int til
     TS(5);
     return succ;
   }
-  if constexpr (EK == 2 && XR == 2 && WR == 2) {
-    // Register epilogue with one residual and the row statistics (proj, fc2: x += ...): the residual
-    // rows are requested first (in the whole-line layout the stores use, below), then the operand
-    // buffers are handed to the next tile's prologue DMA as above.  Output =
-    // fp16(acc + bias) + residual in packed fp16, as the staged epilogue.  Row statistics: (sum, sumsq)
-    // of the stored fp16 values per lane, over the 4 lanes of a row by permlane swaps, over the 4 waves
-    // of a 256-column block through an 8-KiB LDS table.
-    const vda_epilogue& e = p.epi;
-    const int g = lane >> 4;
-    const long mrows = p.M - m0;
-    auto rsrc_rows = [&](const void* base, long ld) {
-      return __builtin_amdgcn_make_buffer_rsrc((void*)((const h16*)base + (long)m0 * ld), (short)0,
-                                               (int)(mrows * ld * 2 < 0x7fffffffL ? mrows * ld * 2 : 0x7fffffffL), 0x00020000);
-    };
-    int ccol[2];
-    bool cok[2];
-#pragma unroll
-    for (int pp = 0; pp < 2; ++pp) {
-      ccol[pp] = n0 + wn * 64 + 32 * pp + 16 * (g & 1) + 8 * (g >> 1);
-      cok[pp] = ccol[pp] < p.N;
-    }
-    // Whole 128-B lines, as the EK 1 epilogue: after the permlane swap a lane holds 8 consecutive
-    // channels of its row mcol; a DPP row_ror:8 exchange between lanes l and l ^ 8 then gives every lane
-    // 8 channels of row mcol & 7 (A) and of row 8 + (mcol & 7) (B) at one column offset, so each 16-B
-    // store (and each residual load, requested in that layout up front) covers whole lines.
-    const bool lo8 = (mcol & 8) == 0;
-    const int colx = lo8 ? ccol[0] : ccol[1];
-    const bool cokx = lo8 ? cok[0] : cok[1];
-    const __amdgpu_buffer_rsrc_t rr = rsrc_rows(e.res, e.ldres);
-    h8 rv[8][2];
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-#pragma unroll
-      for (int ab = 0; ab < 2; ++ab) {
-        const long row = wm * 128 + j * 16 + (mcol & 7) + 8 * ab;
-        const unsigned o = cokx ? (unsigned)((row * e.ldres + colx) * 2) : 0x80000000u;
-        rv[j][ab] = __builtin_bit_cast(h8, __builtin_amdgcn_raw_buffer_load_b128(rr, o, 0, 0));
-      }
-    __builtin_amdgcn_s_barrier();  // every wave is done reading the operand buffers
-    if constexpr (!CONV) {
-      if (vb_next >= 0) {
-        int tmn, tnn;
-        tile_coords(vb_next, tiles_m * tiles_n, tiles_m, tiles_n, tmn, tnn);
-        unsigned xn[XR][2], wn2[WR][2];
-        dense_offsets(tmn * BM, tnn * BN, xn, wn2);
-        chain_dma(xn, wn2);
-      }
-    }
-    static_assert(phased_nit<XR, WR, ACT>() == 16, "the register epilogue issues 16 stores per lane");
-    const __amdgpu_buffer_rsrc_t ry = rsrc_rows(p.y, p.ldy);
-    float* red = reinterpret_cast<float*>(smem + 2 * BUF);  // [4 wn][256 rows][2]
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int rl = wm * 128 + j * 16 + mcol;
-      u32x4 A, B;
-      pack_row_lines([&](int i, int r) { return acc[i][j][r] + pbv[i][r]; }, lo8, A, B);
-      const h8 tA = __builtin_bit_cast(h8, A) + rv[j][0];
-      const h8 tB = __builtin_bit_cast(h8, B) + rv[j][1];
-      const unsigned rA = cokx ? (unsigned)(((long)(wm * 128 + j * 16 + (mcol & 7)) * p.ldy + colx) * 2) : 0x80000000u;
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, tA), ry, rA, 0, VDA_EPI_STORE_AUX);
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, tB), ry, rA + (unsigned)(8 * p.ldy * 2), 0,
-                                             VDA_EPI_STORE_AUX);
-      float sA, qA, sB, qB;
-      stat_acc(cokx ? tA : h8{0, 0, 0, 0, 0, 0, 0, 0}, sA, qA);
-      stat_acc(cokx ? tB : h8{0, 0, 0, 0, 0, 0, 0, 0}, sB, qB);
-      // lane l keeps row mcol (l < 8 of its 16: A, else B) and adds its partner l ^ 8's piece of that row
-      float ssum = (lo8 ? sA : sB) + dpp_f<0x128>(lo8 ? sB : sA);
-      float ssq = (lo8 ? qA : qB) + dpp_f<0x128>(lo8 ? qB : qA);
-      // the row's 64 channels of this wave sit in lanes mcol, mcol + 16, + 32, + 48
-      float x0, x1;
-      swap16_pair(ssum, x0, x1); ssum = x0 + x1;
-      swap16_pair(ssq, x0, x1); ssq = x0 + x1;
-      swap32_pair(ssum, x0, x1); ssum = x0 + x1;
-      swap32_pair(ssq, x0, x1); ssq = x0 + x1;
-      if (g == 0) lds_st_f2(red + 2 * (wn * 256 + rl), make_float2(ssum, ssq));  // asm: no LDS-DMA vmcnt
-    }
-    __builtin_amdgcn_s_waitcnt(0xC07F);
-    __builtin_amdgcn_s_barrier();
-    {  // thread -> (row, statistic): the 4 column-slices of the 256-column block, in a fixed order
-      const int row = tid >> 1, st = tid & 1;
-      const float v = lds_ld_f1(red + 2 * row + st) + lds_ld_f1(red + 2 * (256 + row) + st) +
-                      lds_ld_f1(red + 2 * (512 + row) + st) + lds_ld_f1(red + 2 * (768 + row) + st);
-      const int P = (p.N + 255) / 256;
-      const int m = m0 + row;
-      const __amdgpu_buffer_rsrc_t rs =
-          __builtin_amdgcn_make_buffer_rsrc((void*)e.stats_out, (short)0, (int)((long)p.M * P * 8), 0x00020000);
-      const unsigned vo = m < p.M ? (unsigned)((((long)m * P + (n0 >> 8)) * 2 + st) * 4) : 0x80000000u;
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rs, vo, 0, 0);
-    }
-    TS(5);
-    return succ;
-  }
   if (rows_store) {
     // LDS-staged epilogue: phase 1 writes t = gamma * act(acc + bias + rowbias) as fp16 into a
     // [256][OW] image (8-byte units XOR-swizzled by row&15: conflict-free both ways); phase 2 reads
@@ -1198,7 +1099,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmParams p, int tiles_m,
   constexpr int BUF = (XR + WR) * 128 * BK;
   constexpr bool TAB = XR == 2 && (ACT == VDA_ACT_GELU || ACT == VDA_ACT_GEGLU);
   // + 64 halves at the end (XR 2): the dynamic schedule's successor slot
-  constexpr int SMEM_HALVES = 2 * BUF + (TAB ? PHI_LDS_HALVES : 0) + (LNF ? 4096 + 1024 : 0) + (EK == 2 ? 4096 : 0) +
+  constexpr int SMEM_HALVES = 2 * BUF + (TAB ? PHI_LDS_HALVES : 0) + (LNF ? 4096 + 1024 : 0) +
                               (EK == 3 ? 2048 : 0) + (XR == 2 ? 64 : 0);
   __shared__ __attribute__((aligned(1024))) h16 smem[SMEM_HALVES];
   const int ntiles = tiles_m * tiles_n;

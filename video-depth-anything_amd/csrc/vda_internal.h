@@ -29,12 +29,7 @@ int vda_launch_conv_reg(const GemmParams& p, hipStream_t st);
 // implicit-GEMM depth tail (3x3 C -> 32 hi/lo rows, ReLU, 1x1, ReLU; fp32 depth) in tile configuration cfg
 int vda_launch_depth_gemm(const GemmParams& p, int cfg, hipStream_t st);
 
-// ---- vda_depth.hip: halo-tiled 3x3 kernels ----
-int vda_depth_halo(const void* U, const void* w1, const float* b1, const float* w2, const float* b2, float* depth,
-                   int BT, int H, int W, int C, hipStream_t st);
-bool vda_depth_halo_fused_serves(int Hs, int Ws, int H, int W, int C);
-int vda_depth_halo_fused(const void* x, const void* w1, const float* b1, const float* w2, const float* b2,
-                         float* depth, int BT, int Hs, int Ws, int H, int W, int C, hipStream_t st);
+// ---- vda_oc1.hip: halo-tiled 3x3 conv, Cout = 128 (output_conv1), plain and with the resize fused ----
 int vda_conv_halo(const void* x, const void* w, void* y, const float* bias, int relu, int BT, int H, int W, int Cin,
                   int Cout, hipStream_t st);
 int vda_conv_halo_fused(const void* x, const void* w, void* y, const float* bias, int relu, int BT, int Hs, int Ws,

@@ -174,7 +174,7 @@ def patch_im2col(img: Tensor, Kp: int, dtype=torch.float16) -> Tensor:
 def depth_head(x: Tensor, w1_split: Tensor, b1: Tensor, w2: Tensor, b2: Tensor, Ho: int, Wo: int) -> Tensor:
     """Depth tail: bilinear resize to (Ho, Wo), 3x3 conv (split-fp16 fp32 weights) -> ReLU -> 1x1 -> ReLU.
     x [BT, H, W, C] fp16; w1_split [64, 3, 3, C] fp16 (hi rows 0..31, lo rows 32..63) -> depth [BT, Ho, Wo] fp32.
-    The resize workspace is allocated only for shapes the fused halo kernel does not serve."""
+    The resize workspace is allocated only for shapes the fused depth conv does not serve."""
     _need(x, torch.float16, "x")
     return _vda().depth_head(x, w1_split, b1, w2, b2, int(Ho), int(Wo))
 
