@@ -12,14 +12,17 @@ CXXFLAGS := --offload-arch=$(ARCH) -O3 -fPIC -std=c++17 -Wall -Wno-unused-result
 
 all: $(PKG)/libvda.so $(PKG)/libvda_torch.so
 
-# attention: no NaN inputs by construction, so max chains need no IEEE quieting (v_max3 straight
-# off the MFMA results instead of canonicalising v_max per score); no SLP packing of the softmax sums
-# into v_pk_add_f32 (slower beside MFMAs: spatial attention 303 -> 292 us without it)
-build/vda_attn.o: EXTRA := -fno-honor-nans -mno-amdgpu-ieee -fno-slp-vectorize
+# attention: no NaN inputs by construction; -fno-honor-nans alone lets the max chains compile to v_max3
+# straight off the MFMA results (no canonicalising v_max per score).  -mno-amdgpu-ieee used to stand
+# here too: it changed nothing in the spatial kernel but the mode bit, and it kept every device-library
+# call of the file (threadIdx, powf, sincosf) from being inlined (profiles/attn_selfcontained_isa.log).
+# No SLP packing of the softmax sums into v_pk_add_f32 (slower beside MFMAs: spatial attention 303 -> 292 us
+# without it)
+build/vda_attn.o: EXTRA := -fno-honor-nans -fno-slp-vectorize
 # GEMM epilogues: SLP packing of scalar f32 math needs register moves that cost more than it saves
 build/vda_gemm.o: EXTRA := -fno-slp-vectorize
 
-build/tune/vda_attn.o: EXTRA := -fno-honor-nans -mno-amdgpu-ieee -fno-slp-vectorize
+build/tune/vda_attn.o: EXTRA := -fno-honor-nans -fno-slp-vectorize
 build/tune/vda_gemm.o: EXTRA := -fno-slp-vectorize
 DEPS := $(addprefix $(PKG)/csrc/,vda_common.h vda_stream.h vda_halo.h vda_internal.h vda_tune.h vda_gemm_tile.h vda_gemm_phased.h vda_preprocess.h phi_table.h) include/vda.h include/vda_tune.h
 

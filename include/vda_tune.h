@@ -29,8 +29,9 @@ int vda_debug_hconv(int32_t mode);
  * a materialised resize (bit-identical; needs the workspace).  Any other value is refused (non-zero return,
  * knob unchanged). */
 int vda_debug_dconv(int32_t mode);
-/* Attention kernels: spatial 1 = the round-1 16x16x32 kernel; temporal 1 = the direct-load kernel. */
-int vda_debug_attn(int32_t spatial_old, int32_t temporal_old);
+/* Temporal attention: 1 = the direct-load kernel for every head dim (0 = automatic: the LDS-staged one
+ * where it applies). */
+int vda_debug_attn(int32_t temporal_direct);
 
 #ifdef __cplusplus
 }

@@ -596,15 +596,15 @@ def test_conv_transpose_pixel_shuffle_edges(BT, hh, ww, cout, k):
 # =====================================================================================================
 # Attention
 # =====================================================================================================
-@pytest.mark.parametrize("old", [0, 1], ids=["mfma32", "round1"])
+@pytest.mark.parametrize("old", [0], ids=["mfma32"])
 @pytest.mark.parametrize("N", [1, 31, 32, 33, 63, 64, 65, 127, 128, 129, 257])
 def test_spatial_attention_edges(N, old):
     """Spatial attention (128-query blocks, 64-key tiles, 32-key softmax halves) with sequence lengths on both
     sides of every one of those sizes, H in {1, 3}, B = 2 with batch 0 all NaN: batch 1 is finite, inside the
     bound (fp16_bounds.spatial_attn_ref_bound: P rounded to fp16 before the PV MFMA, the output to fp16, q *
     scale * log2e to fp16) and bit-identical to the call on batch 1 alone; every output sits between sentinel
-    guards that must stay intact (no store past the last query row).  old = 1: the round-1 16x16x32
-    kernel (attn knob)."""
+    guards that must stay intact (no store past the last query row).  The single-valued `old` axis keeps the
+    test ids of the time when a second spatial kernel ran here."""
     T = tune_lib()
     worst = 0.0
     for H in (1, 3):
@@ -615,19 +615,17 @@ def test_spatial_attention_edges(N, old):
         ref_q = (torch.softmax(t[0] @ t[1].transpose(-1, -2) * 0.125, -1) @ t[2]).transpose(1, 2).reshape(N, H * 64)
         buf2, y2 = guarded((2 * N, H * 64))
         buf1, y1 = guarded((N, H * 64))
-        with T.route(attn=(old, 0)):
-            T.spatial_attention(h(both), 2, N, H, out=y2)
-            T.spatial_attention(h(one), 1, N, H, out=y1)
+        T.spatial_attention(h(both), 2, N, H, out=y2)
+        T.spatial_attention(h(one), 1, N, H, out=y1)
         assert guard_ok(buf2) and guard_ok(buf1), "a store outside the output"
-        if not old:
-            assert torch.equal(ops.spatial_attention(h(one), 1, N, H, 64), y1)
-        worst = max(worst, assert_elementwise(y2[N:], ref, bound, f"spatial attention N={N} H={H} old={old}"))
+        assert torch.equal(ops.spatial_attention(h(one), 1, N, H, 64), y1)
+        worst = max(worst, assert_elementwise(y2[N:], ref, bound, f"spatial attention N={N} H={H}"))
         assert rel(y2[N:], ref_q) < BAR_ATTN
         assert torch.equal(y2[N:], y1), "batch 1 depends on batch 0"
-    note(f"spatial attention N={N} old={old}", worst)
+    note(f"spatial attention N={N}", worst)
 
 
-@pytest.mark.parametrize("old", [0, 1], ids=["mfma32", "round1"])
+@pytest.mark.parametrize("old", [0], ids=["mfma32"])
 @pytest.mark.parametrize("ramp", ["up", "spike", "down"])
 def test_spatial_attention_ramps_elementwise(ramp, old):
     """The three score profiles of test_spatial_attention_rebase (climbing, one late spike, falling: the deferred
@@ -637,12 +635,11 @@ def test_spatial_attention_ramps_elementwise(ramp, old):
     qkv = fb.attn_ramp_qkv(ramp, B, N, H)
     ref, bound = fb.spatial_attn_ref_bound(qkv, B, N, H)
     buf, y = guarded((B * N, H * 64))
-    with T.route(attn=(old, 0)):
-        T.spatial_attention(h(qkv), B, N, H, out=y)
+    T.spatial_attention(h(qkv), B, N, H, out=y)
     assert guard_ok(buf), "a store outside the output"
-    worst = assert_elementwise(y, ref, bound, f"spatial attention ramp {ramp} old={old}")
+    worst = assert_elementwise(y, ref, bound, f"spatial attention ramp {ramp}")
     assert rel(y, ref) < BAR_ATTN
-    note(f"spatial attention ramp {ramp} old={old}", worst)
+    note(f"spatial attention ramp {ramp}", worst)
 
 
 TEMPORAL = [(32, 4, 0), (64, 4, 0), (128, 4, 0),                 # the LDS-staged kernel (H % waves-per-block == 0)
@@ -669,7 +666,7 @@ def test_temporal_attention_edges(D, H, old, rope):
         ref, bound = fb.temporal_attn_ref_bound(one, 1, Tn, 1, H, D, rope)
         buf3, y3 = guarded((Tn * S, C))
         buf1, y1 = guarded((Tn, C))
-        with T.route(attn=(0, old)):
+        with T.route(attn=old):
             T.temporal_attention(h(three.reshape(Tn * S, 3 * C)), 1, Tn, S, H, D, rope, out=y3)
             T.temporal_attention(h(one), 1, Tn, 1, H, D, rope, out=y1)
         assert guard_ok(buf3) and guard_ok(buf1), "a store outside the output"
@@ -680,3 +677,28 @@ def test_temporal_attention_edges(D, H, old, rope):
         assert rel(y3[:, 1], ref) < BAR_ATTN
         assert torch.equal(y3[:, 1], y1), "site 1 depends on its neighbour sites"
     note(f"temporal attention D={D} H={H} old={old} rope={rope}", worst)
+
+
+@pytest.mark.parametrize("rope", [0.0, 10000.0])
+@pytest.mark.parametrize("D,H", [(32, 4), (128, 2), (24, 3)])
+def test_temporal_attention_batch_decode(D, H, rope):
+    """The (item -> batch, site, head) decode both temporal kernels share, at B = 2 (the edges test has B = 1
+    only), T = 5, S = 2: both block shapes of the LDS-staged kernel (4 waves at D = 32, 2 at D = 128) and the
+    direct-load kernel (D = 24, H = 3: 6 items in the B = 1 call, so two idle waves in its last block).  Batch 0
+    is all NaN: batch 1 is finite, inside the bound and bit-identical to the B = 1 call on batch 1 alone; both
+    outputs sit between sentinel guards."""
+    T = tune_lib()
+    B, Tn, S, C = 2, 5, 2, H * D
+    one = fb.rnd16(Tn * S, 3 * C, seed=D + H) * 2            # [(1 * T) * S, 3C]: batch 1 alone
+    both = torch.cat([torch.full_like(one, float("nan")), one])
+    ref, bound = fb.temporal_attn_ref_bound(one, 1, Tn, S, H, D, rope)
+    buf2, y2 = guarded((B * Tn * S, C))
+    buf1, y1 = guarded((Tn * S, C))
+    T.temporal_attention(h(both), B, Tn, S, H, D, rope, out=y2)
+    T.temporal_attention(h(one), 1, Tn, S, H, D, rope, out=y1)
+    assert guard_ok(buf2) and guard_ok(buf1), "a store outside the output"
+    got = y2[Tn * S:]
+    assert bool(torch.isfinite(got).all()), "NaN batch 0 reached batch 1"
+    worst = assert_elementwise(got, ref, bound, f"temporal attention B=2 D={D} H={H} rope={rope}")
+    assert torch.equal(got, y1), "batch 1 depends on batch 0"
+    note(f"temporal attention batch decode D={D} H={H} rope={rope}", worst)

@@ -34,7 +34,7 @@ def _attn_scale(D):
 
 
 class TuneLib:
-    DEFAULTS = dict(force_tile=-1, strip_split=0, hconv=-1, dconv=-1, attn=(0, 0), gemm_sched=-1)
+    DEFAULTS = dict(force_tile=-1, strip_split=0, hconv=-1, dconv=-1, attn=0, gemm_sched=-1)
 
     def __init__(self, path):
         self.lib = ctypes.CDLL(path)
@@ -43,8 +43,7 @@ class TuneLib:
 
     def set(self, **knobs):
         for k, v in knobs.items():
-            fn = getattr(self.lib, "vda_debug_" + k)
-            assert (fn(*v) if isinstance(v, tuple) else fn(v)) == 0
+            assert getattr(self.lib, "vda_debug_" + k)(v) == 0
 
     @contextlib.contextmanager
     def route(self, **knobs):

@@ -1,22 +1,32 @@
-"""In-process A/B of the spatial attention across libvda builds (tuning tool, not product code).
+"""In-process A/B of the attention kernels across libvda builds (tuning tool, not product code).
 
-usage: python tools/ab_attn.py LIB_A.so[@K] [LIB_B.so[@K] ...] [--rounds R]
-(@K: a tuning-build library with vda_debug_attn(K, 0) set, e.g. build/tune/libvda.so@2 = the v2 kernel)
-ViT-L clip shape (32 frames x 1370 tokens x 16 heads x 64) through the C ABI (vda_spatial_attention)
-on the current torch stream; rounds alternate the libraries; outputs compared bit-for-bit against the
-first library's and (first 2 frames) against torch SDPA in fp32.
+usage: python tools/ab_attn.py [spatial|temporal|bits] LIB_A.so [LIB_B.so ...] [--rounds R]
+Every case goes through the C ABI on the current torch stream; outputs are compared bit-for-bit against
+the first library's; timing rounds alternate the libraries (median / min / max us per call over the rounds).
+  spatial   ViT-L clip shape (32 frames x 1370 tokens x 16 heads x 64), also against torch SDPA in fp32
+            (first 2 frames)
+  temporal  the four motion-module shapes (T = 32, H = 8, C in {1024, 256}), rope_theta 0 and 10000
+  bits      no timing: the small shapes of tests/test_gpu_fp16_edges.py (spatial N x H and the three ramps,
+            temporal (D, H) x T x S = 3, RoPE off and on) and the shapes above
 """
 import ctypes
 import os
 import statistics
 import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.join(REPO, "tests"))
 import torch
 import torch.nn.functional as F
 from vda_amd import _lib
 
+MODEL_TEMPORAL = [("mm0 37^2 C=1024", 37 * 37, 1024), ("mm1 19^2 C=1024", 19 * 19, 1024),
+                  ("mm2 37^2 C=256", 37 * 37, 256), ("mm3 74^2 C=256", 74 * 74, 256)]
+SMALL_TEMPORAL = [(32, 4), (64, 4), (128, 4), (8, 3), (24, 3), (48, 3), (120, 3), (64, 3), (32, 3)]  # (D, H)
+
 args = sys.argv[1:]
+mode = args.pop(0) if args and args[0] in ("spatial", "temporal", "bits") else "spatial"
 rounds = 7
 libs = []
 i = 0
@@ -27,39 +37,81 @@ while i < len(args):
         libs.append(args[i]); i += 1
 L = []
 for p in libs:
-    path, _, knob = p.partition("@")
-    l = ctypes.CDLL(os.path.abspath(path))
+    l = ctypes.CDLL(os.path.abspath(p))
     _lib._declare(l)
-    if knob:
-        assert l.vda_debug_attn(int(knob), 0) == 0
     L.append(l)
-B, N, H, D = 32, 1370, 16, 64
-torch.manual_seed(0)
-qkv = (torch.randn(B * N, 3 * H * D, device="cuda") * 1.5).half()
 st = torch.cuda.current_stream().cuda_stream
-scale = D ** -0.5
-q, k, v = qkv.view(B, N, 3, H, D)[:2].float().permute(2, 0, 3, 1, 4)
-ref = F.scaled_dot_product_attention(q, k, v).transpose(1, 2).reshape(2 * N, H * D)
-outs = []
-for l in L:
-    y = torch.empty(B * N, H * D, device="cuda", dtype=torch.float16)
-    assert l.vda_spatial_attention(qkv.data_ptr(), y.data_ptr(), B, N, H, D, scale, st) == 0, l.vda_last_error()
-    torch.cuda.synchronize()
-    outs.append(y)
-errs = [float((o[:2 * N].float() - ref).abs().sum() / ref.abs().sum()) for o in outs]
-same = [bool(torch.equal(outs[0], o)) for o in outs[1:]]
-times = [[] for _ in L]
-n = 10
-for r in range(rounds):
-    for li, l in enumerate(L):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(n):
-            l.vda_spatial_attention(qkv.data_ptr(), outs[li].data_ptr(), B, N, H, D, scale, st)
-        e1.record()
+
+
+def spatial(qkv, B, N, H):
+    def call(l, y):
+        assert l.vda_spatial_attention(qkv.data_ptr(), y.data_ptr(), B, N, H, 64, 64 ** -0.5, st) == 0, l.vda_last_error()
+    return call, (B * N, H * 64)
+
+
+def temporal(qkv, B, T, S, H, D, rope):
+    def call(l, y):
+        assert l.vda_temporal_attention(qkv.data_ptr(), y.data_ptr(), B, T, S, H, D, D ** -0.5, rope, st) == 0, l.vda_last_error()
+    return call, (B * T * S, H * D)
+
+
+def run(name, case, timed, n=10):
+    """One case on every library: bit-for-bit against the first, then (timed) alternating rounds."""
+    call, shape = case
+    outs = []
+    for l in L:
+        y = torch.full(shape, float("nan"), device="cuda", dtype=torch.float16)
+        call(l, y)
         torch.cuda.synchronize()
-        times[li].append(e0.elapsed_time(e1) / n * 1e3)
-fl = 4.0 * B * H * N * N * D
-for p, t, e in zip(libs, times, errs):
-    print(f"{p}: med {statistics.median(t):6.1f} us  min {min(t):6.1f} us  {fl / statistics.median(t) / 1e6:6.1f} TF  rel-L1 vs SDPA {e:.2e}", flush=True)
-print("bit-identical to the first:", same, flush=True)
+        outs.append(y)
+    same = [bool(torch.equal(outs[0], o)) for o in outs[1:]]
+    finite = bool(torch.isfinite(outs[0]).all())
+    if timed:
+        times = [[] for _ in L]
+        for r in range(rounds):
+            for li, l in enumerate(L):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(n):
+                    call(l, outs[li])
+                e1.record()
+                torch.cuda.synchronize()
+                times[li].append(e0.elapsed_time(e1) / n * 1e3)
+        for p, t in zip(libs, times):
+            print(f"{name}: {p}: med {statistics.median(t):7.1f} us  min {min(t):7.1f}  max {max(t):7.1f}", flush=True)
+    print(f"{name}: finite {finite}, bit-identical to the first: {same}", flush=True)
+    return outs, all(same) and finite
+
+
+ok = True
+if mode in ("spatial", "bits"):
+    B, N, H = 32, 1370, 16
+    torch.manual_seed(0)
+    qkv = (torch.randn(B * N, 3 * H * 64, device="cuda") * 1.5).half()
+    outs, good = run(f"spatial ViT-L {B}x{N}x{H}x64", spatial(qkv, B, N, H), mode == "spatial")
+    ok &= good
+    q, k, v = qkv.view(B, N, 3, H, 64)[:2].float().permute(2, 0, 3, 1, 4)
+    ref = F.scaled_dot_product_attention(q, k, v).transpose(1, 2).reshape(2 * N, H * 64)
+    print("rel-L1 vs SDPA:", ["%.2e" % float((o[:2 * N].float() - ref).abs().sum() / ref.abs().sum()) for o in outs], flush=True)
+if mode in ("temporal", "bits"):
+    for name, S, C in MODEL_TEMPORAL:
+        for rope in (0.0, 10000.0):
+            torch.manual_seed(S + C)
+            qkv = torch.randn(32 * S, 3 * C, device="cuda", dtype=torch.float16)
+            ok &= run(f"temporal {name} rope={rope:g}", temporal(qkv, 1, 32, S, 8, C // 8, rope), mode == "temporal", n=20)[1]
+if mode == "bits":
+    import fp16_bounds as fb
+    for N in (1, 31, 32, 33, 63, 64, 65, 127, 128, 129, 257):
+        for H in (1, 3):
+            qkv = fb.rnd16(2 * N, 3 * H * 64, seed=N + H).to("cuda", torch.float16)
+            ok &= run(f"spatial N={N} H={H}", spatial(qkv, 2, N, H), False)[1]
+    for ramp in ("up", "spike", "down"):
+        qkv = fb.attn_ramp_qkv(ramp, 2, 129, 2).to("cuda", torch.float16)
+        ok &= run(f"spatial ramp {ramp}", spatial(qkv, 2, 129, 2), False)[1]
+    for D, H in SMALL_TEMPORAL:
+        for T in (1, 2, 31, 32):
+            for rope in (0.0, 10000.0):
+                qkv = (fb.rnd16(T * 3, 3 * H * D, seed=T + D) * 2).to("cuda", torch.float16)
+                ok &= run(f"temporal D={D} H={H} T={T} S=3 rope={rope:g}", temporal(qkv, 1, T, 3, H, D, rope), False)[1]
+print("ALL BIT-IDENTICAL AND FINITE" if ok else "DIFFERENCES (see above)", flush=True)
+sys.exit(0 if ok else 1)

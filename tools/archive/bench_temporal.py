@@ -5,7 +5,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 import torch
 from vda_amd import ops, _lib
 if os.environ.get("VDA_TA_OLD"):
-    _lib.lib().vda_debug_attn(0, 1)
+    _lib.lib().vda_debug_attn(1)
 
 
 def t(fn, n=20):

@@ -8,7 +8,7 @@ D=build/ts; mkdir -p $D
 /opt/rocm/bin/hipcc $FL -DVDA_TS -c video-depth-anything_amd/csrc/vda_hconv.hip -o $D/vda_hconv.o
 /opt/rocm/bin/hipcc $FL -DVDA_TS -c video-depth-anything_amd/csrc/vda_oc1.hip -o $D/vda_oc1.o
 /opt/rocm/bin/hipcc $FL -DVDA_TS -c video-depth-anything_amd/csrc/vda_dconv.hip -o $D/vda_dconv.o
-/opt/rocm/bin/hipcc $FL -fno-honor-nans -mno-amdgpu-ieee -fno-slp-vectorize -DVDA_TS -c video-depth-anything_amd/csrc/vda_attn.hip -o $D/vda_attn.o
+/opt/rocm/bin/hipcc $FL -fno-honor-nans -fno-slp-vectorize -DVDA_TS -c video-depth-anything_amd/csrc/vda_attn.hip -o $D/vda_attn.o
 objs=$(ls build/*.o | grep -v "/vda_gemm.o" | grep -v "/vda_hconv.o" | grep -v "/vda_oc1.o" | grep -v "/vda_dconv.o" | grep -v "/vda_attn.o" | grep -v "/vda_torch.o")
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $objs $D/vda_gemm.o $D/vda_hconv.o $D/vda_oc1.o $D/vda_dconv.o $D/vda_attn.o -o $D/libvda.so
 TD=$(python3 -c "import os, torch; print(os.path.dirname(torch.__file__))")

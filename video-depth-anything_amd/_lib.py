@@ -122,7 +122,7 @@ def _declare(lib):
         "vda_debug_strip_split": ([I], I),
         "vda_debug_hconv": ([I], I),
         "vda_debug_dconv": ([I], I),
-        "vda_debug_attn": ([I, I], I),
+        "vda_debug_attn": ([I], I),
     }
     for name, (args, res) in sig.items():
         if name.startswith("vda_debug_") and not hasattr(lib, name):

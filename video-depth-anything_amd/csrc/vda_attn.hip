@@ -19,204 +19,6 @@ extern "C" int vda_debug_attn_clock_stamps(void* host) {
 namespace {
 
 // =============================================================================================
-// Spatial attention, D = 64.  Block = 4 waves x 32 queries = 128 queries of one (batch, head);
-// key/value tiles of 64 rows are staged in LDS (register-staged double buffer).
-//
-// Everything is computed transposed so that a lane owns ONE query column:
-//   Sᵀ = K · Qᵀ     (A = K rows from LDS, B = Q rows held in registers)   -> lane: 16 keys of q
-//   Oᵀ += Vᵀ · Pᵀ   (A = Vᵀ via ds_read_b64_tr_b16 from the row-major V tile, B = P from regs)
-// The Pᵀ accumulator feeds the PV MFMA directly: lane group g holds keys {4g..4g+3} of each
-// 16-key subtile, so the PV k-order is permuted identically on the Vᵀ side (two tr reads per
-// fragment, rows kc*32+4g.. and kc*32+16+4g..).  Oᵀ lanes hold 4 consecutive head channels of
-// one query -> 8-byte output stores and per-lane softmax rescale, no cross-lane traffic except
-// the 4-lane max/sum reductions.
-// =============================================================================================
-constexpr int SD = 64;       // head dim
-constexpr int SQB = 128;     // queries per block
-constexpr int SKB = 64;      // keys per tile
-
-__device__ __forceinline__ int k_swz(int row, int chunk) { return row * 64 + ((chunk ^ ((row >> 1) & 7)) << 3); }
-__device__ __forceinline__ int v_swz(int row, int chunk) { return row * 64 + ((chunk ^ (((row >> 1) & 3) << 1)) << 3); }
-
-__global__ __launch_bounds__(256) void spatial_attn_kernel(const h16* __restrict__ qkv, h16* __restrict__ out,
-                                                           int N, int H, float scale_log2) {
-  __shared__ __attribute__((aligned(16))) h16 sK[2][SKB * SD];
-  __shared__ __attribute__((aligned(16))) h16 sV[2][SKB * SD];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int h = blockIdx.y, b = blockIdx.z;
-  const int C = H * SD;
-  const long ld = 3L * C;
-  const h16* base = qkv + (long)b * N * ld;
-  const int g = lane >> 4, li = lane & 15;
-
-  // Q fragments (B operand), pre-scaled by scale*log2(e) so scores come out in log2 units:
-  // lane holds Q[q = qs*16 + li][d = ks*32 + 8g .. +7]
-  h8 qf[2][2];
-#pragma unroll
-  for (int qs = 0; qs < 2; ++qs) {
-    const int q = blockIdx.x * SQB + wave * 32 + qs * 16 + li;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      h8 t = h8{0, 0, 0, 0, 0, 0, 0, 0};
-      if (q < N) t = __builtin_bit_cast(h8, ldg16(base + (long)q * ld + h * SD + ks * 32 + g * 8));
-#pragma unroll
-      for (int e = 0; e < 8; ++e) t[e] = (h16)((float)t[e] * scale_log2);
-      qf[qs][ks] = t;
-    }
-  }
-
-  f4 o[4][2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) o[i][j] = f4{0.f, 0.f, 0.f, 0.f};
-  float mrun[2] = {0.f, 0.f};
-  // row sums ride on the PV MFMA: an extra 16-row "Vᵀ" block whose rows 0, 4, 8, 12 are ones puts
-  // sum_k P[k][q] into register 0 of every lane group (no VALU adds, rescaled along with O)
-  f4 lsum[2] = {f4{0.f, 0.f, 0.f, 0.f}, f4{0.f, 0.f, 0.f, 0.f}};
-  const h16 one_or_zero = (lane & 3) == 0 ? (h16)1.f : (h16)0.f;
-  const h8 ones = h8{one_or_zero, one_or_zero, one_or_zero, one_or_zero, one_or_zero, one_or_zero, one_or_zero, one_or_zero};
-  bool first = true;
-
-  // staging: each thread moves 2 K chunks and 2 V chunks (16 B) per tile
-  const int srow = tid >> 3, schunk = tid & 7;
-  uint4 rk[2], rv[2];
-  auto gload = [&](int kt) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int key = kt * SKB + srow + 32 * i;
-      if (key < N) {
-        const h16* rp = base + (long)key * ld + h * SD + schunk * 8;
-        rk[i] = ldg16(rp + C);
-        rv[i] = ldg16(rp + 2 * C);
-      } else {
-        rk[i] = make_uint4(0, 0, 0, 0);
-        rv[i] = make_uint4(0, 0, 0, 0);
-      }
-    }
-  };
-  auto sstore = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      *reinterpret_cast<uint4*>(&sK[buf][k_swz(srow + 32 * i, schunk)]) = rk[i];
-      *reinterpret_cast<uint4*>(&sV[buf][v_swz(srow + 32 * i, schunk)]) = rv[i];
-    }
-  };
-
-  // one 64-key tile; MASK only for the last (partial) tile
-  auto tile = [&](int kt, auto mask_tag) {
-    constexpr bool MASK = decltype(mask_tag)::value;
-    const int buf = kt & 1;
-    // ---- Sᵀ = K Qᵀ : s[a][qs] lane holds keys a*16 + 4g + r, query qs*16 + li
-    // the accumulators start at -m (running max, log2 units), so s = q.k*scale - m comes out of the
-    // MFMA chain ready for exp2 (no per-score subtraction)
-    f4 s[4][2];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int qs = 0; qs < 2; ++qs) s[a][qs] = f4{-mrun[qs], -mrun[qs], -mrun[qs], -mrun[qs]};
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-      for (int a = 0; a < 4; ++a) {
-        const h8 kf = *reinterpret_cast<const h8*>(&sK[buf][k_swz(a * 16 + li, ks * 4 + g)]);
-#pragma unroll
-        for (int qs = 0; qs < 2; ++qs) s[a][qs] = mfma16(kf, qf[qs][ks], s[a][qs]);
-      }
-    }
-    if constexpr (MASK) {
-      const int kbase = kt * SKB;
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          if (kbase + a * 16 + 4 * g + r >= N) { s[a][0][r] = -INFINITY; s[a][1][r] = -INFINITY; }
-    }
-    // ---- online softmax (base 2); the O/l rescale is skipped when no row max grew (wave vote)
-    h8 pf[2][2];  // [qs][kc] P fragments (B operand of PV)
-#pragma unroll
-    for (int qs = 0; qs < 2; ++qs) {
-      // 16 scores -> 8 v_max3 (the file is built with -fno-honor-nans -mno-amdgpu-ieee, so no
-      // canonicalising v_max on the MFMA results), then the 4 lane groups via permlane swaps
-      float mx = fmaxf(fmaxf(s[0][qs][0], s[0][qs][1]), s[0][qs][2]);
-      mx = fmaxf(fmaxf(mx, s[0][qs][3]), s[1][qs][0]);
-      mx = fmaxf(fmaxf(mx, s[1][qs][1]), s[1][qs][2]);
-      mx = fmaxf(fmaxf(mx, s[1][qs][3]), s[2][qs][0]);
-      mx = fmaxf(fmaxf(mx, s[2][qs][1]), s[2][qs][2]);
-      mx = fmaxf(fmaxf(mx, s[2][qs][3]), s[3][qs][0]);
-      mx = fmaxf(fmaxf(mx, s[3][qs][1]), s[3][qs][2]);
-      mx = fmaxf(mx, s[3][qs][3]);
-      mx = group_max4(mx);
-      // mx is the tile max relative to the running max.  Deferred rescale (T13): keep the stale
-      // max while mx <= 8, i.e. P <= 2^8, exact in fp16 P / fp32 sums.  The first tile always
-      // re-bases (m starts at 0, not at a real max).
-      if (first || __any(mx > 8.f)) {
-        const float sh = first ? mx : fmaxf(mx, 0.f);
-        const float alpha = __builtin_amdgcn_exp2f(-sh);
-        mrun[qs] += sh;
-        lsum[qs][0] *= alpha;
-#pragma unroll
-        for (int d = 0; d < 4; ++d) o[d][qs] *= alpha;
-#pragma unroll
-        for (int a = 0; a < 4; ++a) s[a][qs] -= sh;
-      }
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) pf[qs][a >> 1][(a & 1) * 4 + r] = (h16)__builtin_amdgcn_exp2f(s[a][qs][r]);
-    }
-    // ---- Oᵀ += Vᵀ Pᵀ
-    const int q4 = li >> 2, p4 = li & 3;
-#pragma unroll
-    for (int kc = 0; kc < 2; ++kc) {
-#pragma unroll
-      for (int d = 0; d < 4; ++d) {
-        // lane 4q+p of group g: row kc*32 + 4g + q, cols d*16 + 4p
-        const int col = d * 16 + 4 * p4;
-        const int r0 = kc * 32 + 4 * g + q4, r1 = r0 + 16;
-        const h4 v0 = lds_read_tr16(&sV[buf][v_swz(r0, col >> 3) + (col & 7)]);
-        const h4 v1 = lds_read_tr16(&sV[buf][v_swz(r1, col >> 3) + (col & 7)]);
-        const h8 vf = h8{v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-#pragma unroll
-        for (int qs = 0; qs < 2; ++qs) o[d][qs] = mfma16(vf, pf[qs][kc], o[d][qs]);
-      }
-#pragma unroll
-      for (int qs = 0; qs < 2; ++qs) lsum[qs] = mfma16(ones, pf[qs][kc], lsum[qs]);
-    }
-  };
-
-  const int ntiles = (N + SKB - 1) / SKB;
-  const int nfull = N / SKB;
-  gload(0);
-  sstore(0);
-  __syncthreads();
-  for (int kt = 0; kt < ntiles; ++kt) {
-    if (kt + 1 < ntiles) gload(kt + 1);
-    if (kt < nfull) tile(kt, std::false_type{});
-    else tile(kt, std::true_type{});
-    first = false;
-    if (kt + 1 < ntiles) sstore((kt + 1) & 1);
-    __syncthreads();
-  }
-  // ---- epilogue: normalise and store (lane: d = dsub*16 + 4g + r, q = qs*16 + li)
-#pragma unroll
-  for (int qs = 0; qs < 2; ++qs) {
-    const float inv = 1.f / lsum[qs][0];
-    const int q = blockIdx.x * SQB + wave * 32 + qs * 16 + li;
-    if (q < N) {
-      h16* op = out + ((long)b * N + q) * C + h * SD;
-#pragma unroll
-      for (int d = 0; d < 4; ++d) {
-        h4 v;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = (h16)(o[d][qs][r] * inv);
-        *reinterpret_cast<h4*>(op + d * 16 + 4 * g) = v;
-      }
-    }
-  }
-}
-
-// =============================================================================================
 // Spatial attention, D = 64, v_mfma_f32_32x32x16_f16 (the 32-cycle MFMA leaves 24 issue cycles per
 // gap for the softmax VALU, the 16x16x32 one only 8).  Block = 4 waves x 32 queries of one (batch,
 // head); a wave owns 32 query columns, a lane q = lane & 31 and half hf = lane >> 5.
@@ -247,7 +49,26 @@ __global__ __launch_bounds__(256) void spatial_attn_kernel(const h16* __restrict
 // Earlier rounds: QK of tile t+1 before the softmax of tile t 333 vs 292 us; two 32-query sets per
 // wave 317.8 / 307.8 vs 275.0 us (r05_ab_attn_two_sets.log).
 // =============================================================================================
+constexpr int SD = 64;       // head dim
 constexpr int SA_KT = 64;    // keys per tile
+
+// Stages the spatial kernel and both temporal kernels share: a wave's lane (r32 = lane & 31,
+// hf = lane >> 5) owns query r32 in the 32x32x16 MFMA layouts.
+// One A fragment of Vᵀ: two ds_read_b64_tr_b16, the second 8 key rows below the first (P's k order
+// 8(j>>2) + 4hf + (j&3) within a 16-key slice).
+__device__ __forceinline__ h8 vt_frag(const h16* p0, const h16* p1) {
+  const h4 v0 = lds_read_tr16(p0), v1 = lds_read_tr16(p1);
+  return h8{v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+}
+// An Oᵀ tile dt holds query r32's channels d = dt*32 + 8gq + 4hf .. + 3 in registers 4gq .. 4gq + 3:
+// the first channel of group gq, and the group normalised by inv = 1 / row sum as fp16.
+__device__ __forceinline__ int o_chan(int dt, int gq, int hf) { return dt * 32 + 8 * gq + 4 * hf; }
+__device__ __forceinline__ h4 o_group(const f16x& o, int gq, float inv) {
+  h4 v;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) v[r] = (h16)(o[gq * 4 + r] * inv);
+  return v;
+}
 
 __device__ __forceinline__ int sa_kslot(int row, int c) { return row * 8 + (c ^ ((row >> 1) & 7)); }
 __device__ __forceinline__ int sa_vslot(int row, int c) { return row * 8 + (c ^ (((row >> 1) & 1) << 2)); }
@@ -397,11 +218,8 @@ __global__ __launch_bounds__(256, 4) void spatial_attn32_kernel(const h16* __res
       for (int ps = 0; ps < 2; ++ps) {  // the two output tiles' chains interleaved
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt) {
-          const char* va = vbase + vofs[dt] + (kb * 2 + ps) * 2048;
-          const h4 v0 = lds_read_tr16(reinterpret_cast<const h16*>(va));
-          const h4 v1 = lds_read_tr16(reinterpret_cast<const h16*>(va + 1024));
-          const h8 vf = h8{v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-          o[dt] = mfma32(vf, pf[ps], o[dt]);
+          const h16* va = reinterpret_cast<const h16*>(vbase + vofs[dt] + (kb * 2 + ps) * 2048);
+          o[dt] = mfma32(vt_frag(va, va + 8 * SD), pf[ps], o[dt]);
         }
       }
       __builtin_amdgcn_s_setprio(0);
@@ -434,19 +252,14 @@ __global__ __launch_bounds__(256, 4) void spatial_attn32_kernel(const h16* __res
   }
   if (kt < nfull) tile_any(kt, std::false_type{}, std::false_type{});
   if (tail && ntiles > 1) tile_any(ntiles - 1, std::false_type{}, std::true_type{});
-  // epilogue: lane holds Oᵀ[d = dt*32 + 8gq + 4hf + r][q]
+  // epilogue: channels o_chan(dt, gq, hf), added to op term by term (the constants become store offsets)
   const float inv = 1.f / half_sum(lsum);
   if (q < N) {
     h16* op = out + ((long)b * N + q) * C + h * SD;
 #pragma unroll
     for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
-      for (int gq = 0; gq < 4; ++gq) {
-        h4 v;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = (h16)(o[dt][gq * 4 + r] * inv);
-        *reinterpret_cast<h4*>(op + dt * 32 + 8 * gq + 4 * hf) = v;
-      }
+      for (int gq = 0; gq < 4; ++gq) *reinterpret_cast<h4*>(op + dt * 32 + 8 * gq + 4 * hf) = o_group(o[dt], gq, inv);
   }
   ATSC(1);
 }
@@ -461,13 +274,21 @@ __global__ __launch_bounds__(256, 4) void spatial_attn32_kernel(const h16* __res
 // pe='rope' (attention.py:403-429): rotate the 4 channel pairs of an 8-channel q and k fragment of
 // frame t, first channel c0 (even) of C: angle t * theta^(-2i/C) for pair i, fp32 math on the fp16
 // values (the reference's q.float() complex multiply, type_as back to fp16)
+// (cos, sin) of frame t's angle for pair i.  Deliberately a real function: one copy of the powf / sincosf
+// code in the file instead of one per unrolled site (4x the kernel's code otherwise), no out-pointers
+// and so no scratch, and the RoPE outputs keep their bits: with the math inlined into the kernels some
+// outputs moved in the last place (profiles/attn_selfcontained_bit_identity.log).
+__device__ __noinline__ float2 rope_cs(int t, int i, int C, float theta) {
+  const float freq = 1.f / powf(theta, (float)(2 * i) / (float)C);
+  float sn, cs;
+  sincosf((float)t * freq, &sn, &cs);
+  return make_float2(cs, sn);
+}
 __device__ __forceinline__ void rope_frag(h8& q, h8& k, int t, int c0, int C, float theta) {
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const int i = (c0 >> 1) + j;
-    const float freq = 1.f / powf(theta, (float)(2 * i) / (float)C);
-    float sn, cs;
-    sincosf((float)t * freq, &sn, &cs);
+    const float2 r = rope_cs(t, (c0 >> 1) + j, C, theta);
+    const float cs = r.x, sn = r.y;
     const float qa = (float)q[2 * j], qb = (float)q[2 * j + 1];
     const float ka = (float)k[2 * j], kb = (float)k[2 * j + 1];
     q[2 * j] = (h16)(qa * cs - qb * sn);
@@ -478,6 +299,47 @@ __device__ __forceinline__ void rope_frag(h8& q, h8& k, int t, int c0, int C, fl
 }
 
 __device__ __attribute__((aligned(64))) uint4 g_ta_zero[4];
+
+// ---- the stages both temporal kernels share: they differ in how a K / Q fragment and the V tile
+// are fetched and in how an output tile is stored ----
+// work item -> (batch b, site s, head hh), heads fastest
+__device__ __forceinline__ void ta_item(long item, int S, int H, int& b, int& s, int& hh) {
+  hh = (int)(item % H);
+  const long bs = item / H;
+  s = (int)(bs % S);
+  b = (int)(bs / S);
+}
+// Base-2 softmax of query r32 over the 32 keys of Sᵀ (the lane holds keys (r&3) + 8(r>>2) + 4hf, its
+// partner lane ^ 32 the rest; keys >= T are masked): P as the two B fragments of the PV MFMAs;
+// returns 1 / row sum.
+__device__ __forceinline__ float ta_softmax(f16x acc, int T, int hf, float scale_log2, h8 (&pf)[2]) {
+  float mx = -INFINITY;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int key = (r & 3) + 8 * (r >> 2) + 4 * hf;
+    float t = acc[r] * scale_log2;
+    if (key >= T) t = -INFINITY;
+    acc[r] = t;
+    mx = fmaxf(mx, t);
+  }
+  mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+  float sum = 0.f;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const float p = exp2f(acc[r] - mx);
+    sum += p;
+    pf[r >> 3][r & 7] = (h16)p;
+  }
+  sum += __shfl_xor(sum, 32, 64);
+  return 1.f / sum;
+}
+// Where a lane's tr16 reads of the row-major V tile start for output tile dt, key slice st: 16-lane
+// group grp covers key rows 16st + 4(grp>>1) + q4 (and + 8), columns dt*32 + (grp&1)*16 + 4p4
+__device__ __forceinline__ void ta_vpos(int lane, int dt, int st, int& r0, int& col) {
+  const int grp = lane >> 4, q4 = (lane & 15) >> 2, p4 = lane & 3;
+  r0 = 16 * st + 4 * (grp >> 1) + q4;
+  col = dt * 32 + (grp & 1) * 16 + 4 * p4;
+}
 
 constexpr int VDA_TA_NW = 4;  // waves (heads of one site) per temporal-attention block
 template <int DP>
@@ -491,11 +353,9 @@ __global__ __launch_bounds__(64 * VDA_TA_NW) void temporal_attn_kernel(const h16
   __shared__ __attribute__((aligned(16))) h16 sV[VDA_TA_NW][32 * VSTR];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long item = (long)blockIdx.x * VDA_TA_NW + wave;
-  const long nitems = (long)B * S * H;
-  const bool active = item < nitems;
-  const int hh = active ? (int)(item % H) : 0;
-  const long bs = active ? item / H : 0;
-  const int s = (int)(bs % S), b = (int)(bs / S);
+  const bool active = item < (long)B * S * H;  // the last block's waves past the last item idle as item 0
+  int b, s, hh;
+  ta_item(active ? item : 0, S, H, b, s, hh);
   const int C = H * D;
   const long ld = 3L * C;
   const int r32 = lane & 31, hf = lane >> 5;
@@ -526,55 +386,25 @@ __global__ __launch_bounds__(64 * VDA_TA_NW) void temporal_attn_kernel(const h16
     }
     acc = mfma32(kf, qf, acc);
   }
-  // softmax over keys (lane holds keys (r&3)+8(r>>2)+4hf for query r32; partner lane^32 the rest)
-  float mx = -INFINITY;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int key = (r & 3) + 8 * (r >> 2) + 4 * hf;
-    float t = acc[r] * scale_log2;
-    if (key >= T) t = -INFINITY;
-    acc[r] = t;
-    mx = fmaxf(mx, t);
-  }
-  mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-  float sum = 0.f;
   h8 pf[2];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const float p = exp2f(acc[r] - mx);
-    sum += p;
-    pf[r >> 3][r & 7] = (h16)p;
-  }
-  sum += __shfl_xor(sum, 32, 64);
-  const float inv = 1.f / sum;
+  const float inv = ta_softmax(acc, T, hf, scale_log2, pf);
   __syncthreads();  // V tile visible to the whole wave (all waves reach this)
 
-  const int grp = lane >> 4, li = lane & 15, q4 = li >> 2, p4 = li & 3;
 #pragma unroll
   for (int dt = 0; dt < NDT; ++dt) {
     f16x o = {};
 #pragma unroll
     for (int st = 0; st < 2; ++st) {
-      // tr16 read: group grp -> key rows 16st + 4*(grp>>1) + q4 (+8), cols dt*32 + (grp&1)*16 + 4p4
-      const int col = dt * 32 + (grp & 1) * 16 + 4 * p4;
-      const int r0 = 16 * st + 4 * (grp >> 1) + q4;
-      const h4 v0 = lds_read_tr16(vt + r0 * VSTR + col);
-      const h4 v1 = lds_read_tr16(vt + (r0 + 8) * VSTR + col);
-      const h8 vf = h8{v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-      o = mfma32(vf, pf[st], o);
+      int r0, col;
+      ta_vpos(lane, dt, st, r0, col);
+      o = mfma32(vt_frag(vt + r0 * VSTR + col, vt + (r0 + 8) * VSTR + col), pf[st], o);
     }
-    // lane holds Oᵀ[d = dt*32 + (r&3) + 8(r>>2) + 4hf][q = r32]
     if (active && r32 < T) {
       h16* op = out + ((long)(b * T + r32) * S + s) * C + hh * D;
 #pragma unroll
       for (int gq = 0; gq < 4; ++gq) {
-        const int d = dt * 32 + 8 * gq + 4 * hf;
-        if (d < D) {
-          h4 v;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = (h16)(o[gq * 4 + r] * inv);
-          *reinterpret_cast<h4*>(op + d) = v;
-        }
+        const int d = o_chan(dt, gq, hf);
+        if (d < D) *reinterpret_cast<h4*>(op + d) = o_group(o, gq, inv);
       }
     }
   }
@@ -589,9 +419,11 @@ __global__ __launch_bounds__(64 * VDA_TA_NW) void temporal_attn_kernel(const h16
 // CH = D / 8: conflict-free for the K / Q fragment reads (ds_read_b128 lane groups = 16 rows of one
 // chunk).  The output goes back through the q tile so it is stored as whole row segments too.
 // Waves never share LDS, so the only sync is each wave's own vmcnt + one block barrier.
+// Invariant: H % NW == 0 (vda_temporal_attention launches this kernel for no other H), so B * S * H
+// is a multiple of NW, the grid has exactly B * S * H / NW blocks and every wave has an item.
 template <int D, int NW>
 __global__ __launch_bounds__(64 * NW) void temporal_attn_lds_kernel(const h16* __restrict__ qkv, h16* __restrict__ out,
-                                                                  int B, int T, int S, int H, float scale_log2,
+                                                                  int T, int S, int H, float scale_log2,
                                                                   float rope_theta) {
   constexpr int CH = D / 8;                 // 16-B chunks per row
   constexpr int RPG = 16 / CH;              // rows per 256-B bank line
@@ -601,12 +433,8 @@ __global__ __launch_bounds__(64 * NW) void temporal_attn_lds_kernel(const h16* _
   constexpr int NDT = D / 32;
   __shared__ __attribute__((aligned(16))) h16 sm[NW * 3 * TILE];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const long item = (long)blockIdx.x * NW + wave;
-  const long nitems = (long)B * S * H;
-  const bool active = item < nitems;
-  const int hh = active ? (int)(item % H) : 0;
-  const long bs = active ? item / H : 0;
-  const int s = (int)(bs % S), b = (int)(bs / S);
+  int b, s, hh;
+  ta_item((long)blockIdx.x * NW + wave, S, H, b, s, hh);
   const int C = H * D;
   const long ld = 3L * C;
   h16* tq = sm + wave * 3 * TILE;
@@ -623,14 +451,15 @@ __global__ __launch_bounds__(64 * NW) void temporal_attn_lds_kernel(const h16* _
       const int row = sl / CH;
       const int c = pos(row, sl % CH);
       const void* src = g_ta_zero;
-      if (active && row < T) src = qkv + ((long)(b * T + row) * S + s) * ld + z * C + hh * D + c * 8;
+      if (row < T) src = qkv + ((long)(b * T + row) * S + s) * ld + z * C + hh * D + c * 8;
       __builtin_amdgcn_global_load_lds(src, (VDA_LDS void*)(tq + z * TILE + i * 512), 16, 0, 0);
     }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
-  // Sᵀ = K Qᵀ: lane (r32, hf) holds K / Q row r32, channels st * 16 + hf * 8 .. + 7
+  // Sᵀ = K Qᵀ: lane (r32, hf) holds K / Q row r32, channels st * 16 + hf * 8 .. + 7; rows >= T are
+  // zero in LDS and masked in the softmax
   const int r32 = lane & 31, hf = lane >> 5;
   f16x acc = {};
 #pragma unroll
@@ -641,52 +470,25 @@ __global__ __launch_bounds__(64 * NW) void temporal_attn_lds_kernel(const h16* _
     if (rope_theta > 0.f) rope_frag(qf, kf, r32, hh * D + c * 8, C, rope_theta);
     acc = mfma32(kf, qf, acc);
   }
-  // softmax over keys (lane holds keys (r&3)+8(r>>2)+4hf for query r32; partner lane^32 the rest);
-  // rows >= T are zero in LDS and masked here
-  float mx = -INFINITY;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int key = (r & 3) + 8 * (r >> 2) + 4 * hf;
-    float t = acc[r] * scale_log2;
-    if (key >= T) t = -INFINITY;
-    acc[r] = t;
-    mx = fmaxf(mx, t);
-  }
-  mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-  float sum = 0.f;
   h8 pf[2];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const float p = exp2f(acc[r] - mx);
-    sum += p;
-    pf[r >> 3][r & 7] = (h16)p;
-  }
-  sum += __shfl_xor(sum, 32, 64);
-  const float inv = 1.f / sum;
+  const float inv = ta_softmax(acc, T, hf, scale_log2, pf);
 
-  const int grp = lane >> 4, li = lane & 15, q4 = li >> 2, p4 = li & 3;
 #pragma unroll
   for (int dt = 0; dt < NDT; ++dt) {
     f16x o = {};
 #pragma unroll
     for (int st = 0; st < 2; ++st) {
-      // tr16 read: group grp -> key rows 16st + 4*(grp>>1) + q4 (+8), cols dt*32 + (grp&1)*16 + 4p4
-      const int col = dt * 32 + (grp & 1) * 16 + 4 * p4;
-      const int r0 = 16 * st + 4 * (grp >> 1) + q4;
-      const h4 v0 = lds_read_tr16(tv + r0 * D + pos(r0, col >> 3) * 8 + (col & 7));
-      const h4 v1 = lds_read_tr16(tv + (r0 + 8) * D + pos(r0 + 8, col >> 3) * 8 + (col & 7));
-      const h8 vf = h8{v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-      o = mfma32(vf, pf[st], o);
+      int r0, col;
+      ta_vpos(lane, dt, st, r0, col);
+      o = mfma32(vt_frag(tv + r0 * D + pos(r0, col >> 3) * 8 + (col & 7),
+                         tv + (r0 + 8) * D + pos(r0 + 8, col >> 3) * 8 + (col & 7)), pf[st], o);
     }
-    // lane holds Oᵀ[d = dt*32 + (r&3) + 8(r>>2) + 4hf][q = r32]: into the q tile (its fragments are
-    // consumed) as rows, so the stores below write whole D*2-B row segments
+    // into the q tile (its fragments are consumed) as rows, so the stores below write whole D*2-B
+    // row segments
 #pragma unroll
     for (int gq = 0; gq < 4; ++gq) {
-      const int d = dt * 32 + 8 * gq + 4 * hf;
-      h4 v;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) v[r] = (h16)(o[gq * 4 + r] * inv);
-      *reinterpret_cast<h4*>(tq + r32 * D + pos(r32, d >> 3) * 8 + (d & 7)) = v;
+      const int d = o_chan(dt, gq, hf);
+      *reinterpret_cast<h4*>(tq + r32 * D + pos(r32, d >> 3) * 8 + (d & 7)) = o_group(o, gq, inv);
     }
   }
 #pragma unroll
@@ -694,20 +496,18 @@ __global__ __launch_bounds__(64 * NW) void temporal_attn_lds_kernel(const h16* _
     const int sl = i * 64 + lane;
     const int row = sl / CH, c = sl % CH;
     const uint4 v = *reinterpret_cast<const uint4*>(tq + row * D + pos(row, c) * 8);
-    if (active && row < T) *reinterpret_cast<uint4*>(out + ((long)(b * T + row) * S + s) * C + hh * D + c * 8) = v;
+    if (row < T) *reinterpret_cast<uint4*>(out + ((long)(b * T + row) * S + s) * C + hh * D + c * 8) = v;
   }
 }
 
-// vda_debug_attn (tuning build): the round-1 spatial kernel / the direct-load temporal kernel
-VDA_KNOB(int, g_sa_old, 0);
-VDA_KNOB(int, g_ta_old, 0);
+// vda_debug_attn (tuning build): 1 = the direct-load temporal kernel for every head dim
+VDA_KNOB(int, g_ta_direct, 0);
 
 }  // namespace
 
 #ifdef VDA_TUNING
-extern "C" int vda_debug_attn(int32_t spatial_old, int32_t temporal_old) {
-  g_sa_old = spatial_old;
-  g_ta_old = temporal_old;
+extern "C" int vda_debug_attn(int32_t temporal_direct) {
+  g_ta_direct = temporal_direct;
   return 0;
 }
 #endif
@@ -717,17 +517,11 @@ extern "C" int vda_spatial_attention(const void* qkv, void* out, int32_t B, int3
   VDA_CHECK_ARG(qkv && out, "null pointer");
   VDA_CHECK_ARG(B > 0 && N > 0 && H > 0, "empty attention");
   VDA_CHECK_ARG(D == SD, "spatial attention supports head dim 64 only");
-  if (g_sa_old) {
-    dim3 grid((N + SQB - 1) / SQB, H, B);
-    hipLaunchKernelGGL(spatial_attn_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const h16*)qkv,
-                       (h16*)out, N, H, scale * 1.4426950408889634f);
-  } else {
-    const int nqb = (N + 127) / 128;
-    const long nb = (long)nqb * H * B;
-    VDA_CHECK_ARG(nb < 0x7fffffffL, "attention grid too large");
-    hipLaunchKernelGGL(spatial_attn32_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, (const h16*)qkv,
-                       (h16*)out, N, H, nqb, (int)nb, scale * 1.4426950408889634f);
-  }
+  const int nqb = (N + 127) / 128;
+  const long nb = (long)nqb * H * B;
+  VDA_CHECK_ARG(nb < 0x7fffffffL, "attention grid too large");
+  hipLaunchKernelGGL(spatial_attn32_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, (const h16*)qkv,
+                     (h16*)out, N, H, nqb, (int)nb, scale * 1.4426950408889634f);
   VDA_LAUNCH_CHECK();
   return 0;
 }
@@ -744,18 +538,18 @@ extern "C" int vda_temporal_attention(const void* qkv, void* out, int32_t B, int
   const float sl = scale * 1.4426950408889634f;
   // q / k / v rows staged in LDS for the head dims the model uses (128 at C = 1024, 32 at C = 256, 8
   // heads); the direct-load kernel below serves the other head dims
-  if (!g_ta_old && (D == 32 || D == 64 || D == 128)) {
+  if (!g_ta_direct && (D == 32 || D == 64 || D == 128)) {
     const int nw = D == 128 ? 2 : 4;  // 24 / 12 / 6 KiB of LDS per wave
-    if (H % nw == 0) {
-      const unsigned g = (unsigned)((items + nw - 1) / nw);
+    if (H % nw == 0) {  // the LDS kernel's invariant: no idle wave
+      const unsigned g = (unsigned)(items / nw);
       if (D == 128)
-        hipLaunchKernelGGL((temporal_attn_lds_kernel<128, 2>), dim3(g), dim3(128), 0, st, (const h16*)qkv, (h16*)out, B, T,
+        hipLaunchKernelGGL((temporal_attn_lds_kernel<128, 2>), dim3(g), dim3(128), 0, st, (const h16*)qkv, (h16*)out, T,
                            S, H, sl, rope_theta);
       else if (D == 64)
-        hipLaunchKernelGGL((temporal_attn_lds_kernel<64, 4>), dim3(g), dim3(256), 0, st, (const h16*)qkv, (h16*)out, B, T,
+        hipLaunchKernelGGL((temporal_attn_lds_kernel<64, 4>), dim3(g), dim3(256), 0, st, (const h16*)qkv, (h16*)out, T,
                            S, H, sl, rope_theta);
       else
-        hipLaunchKernelGGL((temporal_attn_lds_kernel<32, 4>), dim3(g), dim3(256), 0, st, (const h16*)qkv, (h16*)out, B, T,
+        hipLaunchKernelGGL((temporal_attn_lds_kernel<32, 4>), dim3(g), dim3(256), 0, st, (const h16*)qkv, (h16*)out, T,
                            S, H, sl, rope_theta);
       VDA_LAUNCH_CHECK();
       return 0;

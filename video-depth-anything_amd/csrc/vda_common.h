@@ -179,12 +179,6 @@ __device__ __forceinline__ void swap32_pair(float v, float& a, float& b) {
 }
 __device__ __forceinline__ float half_max(float v) { float a, b; swap32_pair(v, a, b); return fmaxf(a, b); }
 __device__ __forceinline__ float half_sum(float v) { float a, b; swap32_pair(v, a, b); return a + b; }
-// max over the 4 lane groups of 16 (lane bits 4 and 5) with VALU permlane swaps, no LDS traffic
-__device__ __forceinline__ float group_max4(float v) {
-  float a, b;
-  swap16_pair(v, a, b);
-  return half_max(fmaxf(a, b));
-}
 
 __device__ __forceinline__ uint4 ldg16(const void* p) { return *reinterpret_cast<const uint4*>(p); }
 __device__ __forceinline__ void stg16(void* p, uint4 v) { *reinterpret_cast<uint4*>(p) = v; }
