@@ -65,9 +65,9 @@ typedef struct vda_epilogue {
    * fp16 W actually used), and ln_stats[m] = (mean, rstd) of row m from vda_row_stats.  Then
    * rstd (x W^T - mean colsum) + bias = LN(x) W_ln^T + b exactly in real arithmetic.  Row store only, no gamma, activation none / gelu.
    * With a rowbias (the motion-module q/k/v: LN(x) + pe[t] then to_q/k/v, motion_module.py:175,256,
-   * 263): bias required, no activation / res / res2 / stats_out, rdiv >= 256, N % 256 == 0,
-   * M >= 4096, K % 64 == 0, 16-byte aligned x / y rows (the phased route's EK 3 epilogue; -22
-   * otherwise). */
+   * 263): bias required, no activation / res / res2 / stats_out, rdiv >= 256, N % 256 == 0, 16-byte
+   * aligned x, and a shape the GEMM route gives to the phased 256x256 kernel, whose EK 3 epilogue is
+   * the only one that implements the pair (-22 otherwise; vda_gemm_check answers for a shape). */
   const float* ln_stats;  /* [M, 2] or NULL                                              */
   const float* ln_colsum; /* [N]                                                     */
   /* ln_parts > 0: ln_stats instead holds [M, ln_parts, 2] partial (sum, sum of squares) of row m
@@ -103,7 +103,8 @@ typedef struct vda_epilogue {
    * holds the M - ceil(M / drop_period) patch rows.  For the DPT projects 1x1 conv on a tap with the
    * final LayerNorm folded in (dpt.py:60-68).  Served by the phased route's register epilogue only:
    * drop_period >= 256, ln_stats + ln_colsum + bias, activation none, row store, no gamma / res / res2 /
-   * rowbias / stats_out, N % 256 == 0, M >= 4096, K % 64 == 0, 16-byte aligned Y rows; -22 otherwise. */
+   * rowbias / stats_out, N % 256 == 0, and a shape the GEMM route gives to the phased 256x256 kernel;
+   * -22 otherwise (vda_gemm_check answers for a shape). */
   int32_t drop_period;
 } vda_epilogue;
 
@@ -125,6 +126,12 @@ const char* vda_last_error(void);
  */
 int vda_gemm(const void* x, int64_t ldx, const void* w, void* y, int64_t ldy,
              int32_t M, int32_t N, int32_t K, const vda_epilogue* epi, void* stream);
+/* vda_gemm's argument and route checks without a launch, for 16-byte aligned x / w / y: 0, or the error
+ * vda_gemm would return (message in vda_last_error).  Of each epilogue pointer only whether it is NULL and
+ * its alignment are looked at, so stand-in values will do.  A caller with a choice (drop_period or a
+ * LayerNorm + GEMM pair, ln_stats + rowbias or LayerNorm first) asks here instead of copying the
+ * conditions; vda_gemm itself is this check followed by the launch. */
+int vda_gemm_check(int64_t ldx, int64_t ldy, int32_t M, int32_t N, int32_t K, const vda_epilogue* epi);
 
 /*
  * NHWC implicit-GEMM 2-D convolution, fp16 MFMA, square kernel `ks`, zero padding `pad`.

@@ -14,7 +14,9 @@ extern "C" {
 
 /* GEMM / conv tile configuration (-1 = automatic; 0 = 128x128/4 waves, 1 = 256x128/8 waves,
  * 2 = 128x64/4 waves, 3 = 256x256/8 waves; -2 / -3 = automatic tiles with the strip-tiled 3x3 conv for
- * no / every Cout = 256 shape; 10 + cfg = implicit-GEMM depth tail, which ignores the values below 10). */
+ * no / every Cout = 256 shape; 13 (any value >= 10) = the implicit-GEMM depth tail for every shape, which
+ * has one tile configuration and ignores the values below 10).  6 = 64x64 and 7 = 64x128 exist for the dense
+ * GEMM only; 4 = 256x256 and 5 = 512x128 are the phased kernels. */
 int vda_debug_force_tile(int32_t cfg);
 /* Phased 256-row GEMM: persist_blocks > 0 launches that many persistent blocks (0 = one block per tile,
  * -1 = automatic: one per CU). */

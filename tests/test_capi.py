@@ -285,3 +285,137 @@ def test_groupnorm_linear_routes_and_validation():
     bad = list(args)
     bad[13] = None  # no workspace
     assert lib.vda_groupnorm_linear(*bad, ws, None) == -22
+
+
+def _gemm_both(ldx, ldy, M, N, K, e, msg):
+    """Rejected with `msg` by the query and by vda_gemm itself (fake pointers: no launch happens)."""
+    lib = _lib.lib()
+    fake = ctypes.c_void_p(0x1000)
+    _rejected(lib.vda_gemm_check(ldx, ldy, M, N, K, e), msg)
+    _rejected(lib.vda_gemm(fake, ldx, fake, fake, ldy, M, N, K, e, None), msg)
+
+
+def test_gemm_check_drop_period():
+    """drop_period exists in one kernel, the phased 256x256 route's register LN-fold epilogue: vda_gemm_check
+    accepts the smallest shape that route serves (M = 4096, N = 256, K = 64, frames of 256 rows, LN fold +
+    bias) and refuses every neighbour that another kernel, which stores all M rows, would get."""
+    lib = _lib.lib()
+    E = lambda **kw: _lib.Epilogue(**{**dict(rdiv=1, rmod=1, bias=0x2000, ln_stats=0x3000, ln_colsum=0x4000,  # noqa: E731
+                                             drop_period=256), **kw})
+    assert lib.vda_gemm_check(64, 256, 4096, 256, 64, E()) == 0
+    assert lib.vda_gemm_check(64, 256, 4096, 256, 64, E(ln_parts=1)) == 0
+    msg = b"drop_period"
+    _gemm_both(64, 256, 4095, 256, 64, E(), msg)
+    _gemm_both(64, 264, 4096, 264, 64, E(), msg)
+    _gemm_both(72, 256, 4096, 256, 72, E(), msg)
+    _gemm_both(64, 256, 4096, 256, 64, E(drop_period=255), msg)
+    _gemm_both(64, 260, 4096, 256, 64, E(), msg)
+    _gemm_both(64, 256, 4096, 256, 64, E(res=0x5000, ldres=256), msg)
+    _gemm_both(64, 256, 4096, 256, 64, E(stats_out=0x5000), msg)
+    _gemm_both(64, 256, 4096, 256, 64, E(act=_lib.ACT_GELU), msg)
+
+
+def test_gemm_check_ln_fold_rowbias():
+    """The LN fold with a per-frame row bias exists in one kernel (the phased 256x256 route's EK 3 epilogue):
+    accepted at rdiv = 256, M = 4096, N = 768, K = 256; each neighbour off that route is refused."""
+    lib = _lib.lib()
+    E = lambda **kw: _lib.Epilogue(**{**dict(rdiv=256, rmod=16, bias=0x2000, rowbias=0x5000, ln_stats=0x3000,  # noqa: E731
+                                             ln_colsum=0x4000, ln_parts=1), **kw})
+    assert lib.vda_gemm_check(256, 768, 4096, 768, 256, E()) == 0
+    msg = b"ln_stats with rowbias"
+    _gemm_both(256, 768, 4096, 768, 256, E(rdiv=255), msg)
+    _gemm_both(256, 640, 4096, 640, 256, E(), msg)
+    _gemm_both(96, 768, 4096, 768, 96, E(), msg)
+    _gemm_both(256, 768, 4095, 768, 256, E(), msg)
+    _gemm_both(256, 768, 4096, 768, 256, E(bias=None), msg)
+
+
+def test_gemm_check_ranges_and_null_epilogue():
+    """The phased route addresses X and W with 32-bit byte offsets: M * ldx * 2 and N * K * 2 just below 2^31
+    are accepted, at 2^31 refused (with drop_period, which no other route serves).  A null epilogue is the
+    default one, as in vda_gemm."""
+    lib = _lib.lib()
+    fake = ctypes.c_void_p(0x1000)
+    E = lambda: _lib.Epilogue(rdiv=1, rmod=1, bias=0x2000, ln_stats=0x3000, ln_colsum=0x4000, drop_period=256)  # noqa: E731
+    M = 2 ** 20  # M * ldx * 2 = 2^31 at ldx = 1024
+    assert lib.vda_gemm_check(1024 - 8, 256, M, 256, 64, E()) == 0
+    _gemm_both(1024, 256, M, 256, 64, E(), b"drop_period")
+    N = 2 ** 20  # N * K * 2 = 2^31 at K = 1024
+    assert lib.vda_gemm_check(1024 - 64, N, 4096, N, 1024 - 64, E()) == 0
+    _gemm_both(1024, N, 4096, N, 1024, E(), b"drop_period")
+    assert lib.vda_gemm_check(64, 256, 4096, 256, 64, None) == 0
+    assert lib.vda_gemm_check(64, 256, 100, 24, 64, None) == 0
+    _rejected(lib.vda_gemm_check(64, 256, 4096, 0, 64, None), b"empty GEMM")
+    _rejected(lib.vda_gemm(fake, 64, fake, fake, 256, 4096, 0, 64, None, None), b"empty GEMM")
+    _rejected(lib.vda_gemm_check(60, 256, 4096, 256, 64, None), b"ldx >= K")
+    _rejected(lib.vda_gemm(fake, 60, fake, fake, 256, 4096, 256, 64, None, None), b"ldx >= K")
+
+
+def test_ops_gemm_accepts_matches_and_memoises(monkeypatch):
+    """ops.gemm_accepts gives vda_gemm_check's answers for the features the model uses, and asks the library
+    once per argument tuple."""
+    from vda_amd import ops
+    lib = _lib.lib()
+    calls = []
+    real = lib.vda_gemm_check
+
+    def counting(*a):
+        calls.append(a[:5])
+        return real(*a)
+    monkeypatch.setattr(lib, "vda_gemm_check", counting)
+    ops.gemm_accepts.cache_clear()
+    drop = dict(ln_fold=True, drop_period=256)
+    assert ops.gemm_accepts(4096, 256, 64, **drop)
+    assert len(calls) == 1
+    assert ops.gemm_accepts(4096, 256, 64, **drop)
+    assert len(calls) == 1  # the second call never reached the library
+    assert not ops.gemm_accepts(4095, 256, 64, **drop)
+    assert not ops.gemm_accepts(4096, 264, 64, **drop)
+    assert not ops.gemm_accepts(4096, 256, 72, **drop)
+    assert not ops.gemm_accepts(4096, 256, 64, ln_fold=True, drop_period=255)
+    assert not ops.gemm_accepts(4096, 256, 64, ldy=260, **drop)
+    assert not ops.gemm_accepts(4096, 256, 64, res=True, **drop)
+    assert not ops.gemm_accepts(4096, 256, 64, stats_out=True, **drop)
+    assert not ops.gemm_accepts(4096, 256, 64, act=ops.ACT_GELU, **drop)
+    assert not ops.gemm_accepts(4096, 256, 64, bias=False, **drop)
+    qkv = dict(ln_fold=True, ln_parts=1, rowbias=True, rmod=16)
+    assert ops.gemm_accepts(4096, 768, 256, rdiv=256, **qkv)
+    assert not ops.gemm_accepts(4096, 768, 256, rdiv=255, **qkv)
+    assert not ops.gemm_accepts(4096, 640, 256, rdiv=256, **qkv)
+    assert not ops.gemm_accepts(4096, 768, 96, rdiv=256, **qkv)
+    assert not ops.gemm_accepts(4095, 768, 256, rdiv=256, **qkv)
+    assert not ops.gemm_accepts(4096, 768, 256, rdiv=256, bias=False, **qkv)
+    assert ops.gemm_accepts(2 ** 20, 256, 64, ldx=1016, **drop) and not ops.gemm_accepts(2 ** 20, 256, 64, ldx=1024, **drop)
+    assert ops.gemm_accepts(100, 24, 64, bias=False) and ops.gemm_accepts(4096, 512, 64, act=ops.ACT_GEGLU)
+    n = len(calls)
+    assert ops.gemm_accepts(4096, 768, 256, rdiv=256, **qkv) and len(calls) == n
+    ops.gemm_accepts.cache_clear()  # nothing cached through the wrapper outlives this test
+
+
+def test_model_fold_decisions_on_meta():
+    """Where the model takes the fused epilogues, on meta tensors (only shapes are read): the taps go through
+    the drop_period projects GEMMs for ViT-L at 32 x 518^2 and 32 x 518 x 924, not at 4 x 70 x 98 (frames of
+    36 tokens), not for ViT-S (projects of 48 .. 384 channels) and not with the readout; the motion modules'
+    q/k/v LayerNorm is folded for all four ViT-L modules at 32 x 518^2 (C = 1024 at 37^2 and 19^2 sites,
+    C = 256 at 37^2 and 74^2) and for none at 4 x 70 x 98.  The model asks ops.gemm_accepts; these are the
+    answers of its own copy of the conditions before that."""
+    import torch
+    meta = torch.device("meta")
+
+    def decisions(enc, BT, H, W, **kw):
+        m = vda_amd.VideoDepthAnything.from_config(enc, device="meta", **kw)
+        P = m._pack(meta, False)
+        ph, pw = H // 14, W // 14
+        sites = (ph * pw, ((ph - 1) // 2 + 1) * ((pw - 1) // 2 + 1), ph * pw, 4 * ph * pw)
+        return m._tap_fold(P, BT, ph * pw + 1), [m._qkv_fold(q, BT * S, S, BT) for q, S in zip(P.mm, sites)]
+
+    assert decisions("vitl", 32, 518, 518) == (True, [[True, True]] * 4)
+    assert decisions("vitl", 32, 518, 924) == (True, [[True, True]] * 4)
+    assert decisions("vitl", 4, 70, 98) == (False, [[False, False]] * 4)
+    assert decisions("vits", 4, 518, 518) == (False, [[False, False]] * 4)
+    assert decisions("vitl", 32, 518, 518, use_clstoken=True) == (False, [[True, True]] * 4)
+    # a motion module whose K is no multiple of 64, or past the 32-bit ranges: LayerNorm + GEMM, not an error
+    m = vda_amd.VideoDepthAnything.from_config("vitl", device="meta")
+    q = m._pack(meta, False).mm[2]
+    assert m._qkv_fold(q, 32 * 1369, 1369, 32) == [True, True]
+    assert m._qkv_fold(q, 2 ** 22, 2 ** 17, 32) == [False, False]  # M * C * 2 = 2^31

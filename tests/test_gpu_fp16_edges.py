@@ -189,7 +189,7 @@ def test_gemm_tile_edges(cfg, epi):
 # Dense GEMM, phased kernels (vda_gemm_phased.h): cfg 4 = 256x256, cfg 5 = 512x128
 # =====================================================================================================
 def forced(T, cfg, **knobs):
-    """A launch function for run_gemm(same_as=): the same GEMM with the phased kernel `cfg` forced.  launch_act
+    """A launch function for run_gemm(same_as=): the same GEMM with the phased kernel `cfg` forced.  gemm_route
     only takes the phased 256x256 kernel on its own when M, N, K and every alignment allow it and otherwise
     falls back to a tile kernel with other rounding points, which the (looser) staged bound would not notice;
     bit-identity with the forced kernel over a million outputs shows which kernel the automatic route ran."""
@@ -224,7 +224,7 @@ def test_gemm_phased_edges(M, N):
 @pytest.mark.parametrize("N", [256, 512])
 @pytest.mark.parametrize("epi", ["bias", "gelu", "gamma_res", "res_res2", "rowbias", "geglu", "ps2", "ps4", "strided_x"])
 def test_gemm_phased_epilogues(epi, N):
-    """The register and staged epilogues launch_phased picks without the LayerNorm fold, at M = 4097 (a one-row
+    """The register and staged epilogues gemm_route picks without the LayerNorm fold, at M = 4097 (a one-row
     last M tile), K = 192, on 3 persistent blocks: bias and bias + GELU (EK 1), the general staged epilogue
     (GEGLU; gamma / res / res2: t = gamma * act(..) rounded to fp16, then the residuals added as packed fp16 vectors,
     fp16_bounds.gemm_ref_bound staged=True; GELU and GEGLU through the Phi table; pixel-shuffle store), the
@@ -255,7 +255,7 @@ DROPS = {"ln_drop": 300, "ln_drop256": 256, "ln_drop511": 511, "ln_drop4096": 40
 @pytest.mark.parametrize("N", [256, 512])
 @pytest.mark.parametrize("kind", fb.LN_KINDS + ("ln_drop256", "ln_drop511", "ln_drop4096"))
 def test_gemm_phased_ln_fold(kind, N):
-    """The LayerNorm-fold epilogues of launch_phased at M = 4097, K = 192, 3 persistent blocks: plain with [M, 2]
+    """The LayerNorm-fold epilogues gemm_route picks at M = 4097, K = 192, 3 persistent blocks: plain with [M, 2]
     (mean, rstd) statistics (register epilogue EK 1) and with three-part (sum, sum of squares) statistics, + GELU,
     + GEGLU (staged), + the per-frame row bias (EK 3, frames of 300 rows), + stats_out (the staged epilogue and
     the separate partial-sum pass), and drop_period (served by this route's EK 1 epilogue only; the dropped row

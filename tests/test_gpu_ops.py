@@ -321,6 +321,30 @@ def test_gemm_drop_period_validation():
         ops.gemm(x, w, bias=bb, ln_stats=ops.row_stats(x, 1e-6), ln_colsum=c1, drop_period=141)
 
 
+def test_gemm_accepts_ties_query_to_launch():
+    """The smallest shape the row-drop epilogue exists for (16 frames of 256 rows, N = 256, K = 64):
+    ops.gemm_accepts says yes, ops.gemm(drop_period=256) returns the 4096 - 16 patch rows, bit-identical to
+    the same LN-folded GEMM without drop_period with the cls rows taken out on the host (the same kernel,
+    only the store differs).  Two neighbours the query refuses (4095 rows; frames of 255) raise in ops.gemm."""
+    M, N, K, P = 4096, 256, 64, 256
+    torch.manual_seed(11)
+    x = (torch.randn(M, K, device=DEV) * 2 + 0.5).half()
+    wg = (torch.randn(N, K, device=DEV) * K ** -0.5).half()
+    c1, bb = wg.float().sum(1), torch.randn(N, device=DEV) * 0.1
+    fold = dict(bias=bb, ln_stats=ops.row_stats(x, 1e-6), ln_eps=1e-6, ln_colsum=c1)
+    assert ops.gemm_accepts(M, N, K, ln_fold=True, drop_period=P)
+    y = ops.gemm(x, wg, drop_period=P, **fold)
+    assert y.shape == (M - M // P, N)
+    full = ops.gemm(x, wg, **fold)
+    assert torch.equal(y, full.view(M // P, P, N)[:, 1:].reshape(-1, N))
+    assert not ops.gemm_accepts(M - 1, N, K, ln_fold=True, drop_period=P)
+    with pytest.raises(RuntimeError, match="drop_period"):
+        ops.gemm(x[:M - 1], wg, drop_period=P, **{**fold, "ln_stats": ops.row_stats(x[:M - 1], 1e-6)})
+    assert not ops.gemm_accepts(M, N, K, ln_fold=True, drop_period=P - 1)
+    with pytest.raises(RuntimeError, match="drop_period"):
+        ops.gemm(x, wg, drop_period=P - 1, **fold)
+
+
 @pytest.mark.parametrize("B,N,H", [(2, 200, 3), (1, 1370, 16), (3, 82, 6), (1, 64, 1)])
 def test_spatial_attention(B, N, H):
     D = 64

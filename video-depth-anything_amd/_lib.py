@@ -20,7 +20,8 @@ if os.environ.get("VDA_LIB_OVERRIDE"):  # tuning builds: the op library linked n
 
 # Every symbol include/vda.h declares (checked by tests/test_capi.py).
 EXPORTED = (
-    "vda_version", "vda_epilogue_size", "vda_last_error", "vda_gemm", "vda_conv2d", "vda_conv2d_workspace", "vda_layernorm",
+    "vda_version", "vda_epilogue_size", "vda_last_error", "vda_gemm", "vda_gemm_check", "vda_conv2d", "vda_conv2d_workspace",
+    "vda_layernorm",
     "vda_conv2d_res2_upsample_ok",
     "vda_row_stats", "vda_groupnorm", "vda_groupnorm_workspace",
     "vda_groupnorm_linear", "vda_groupnorm_linear_workspace", "vda_groupnorm_linear_fused",
@@ -77,6 +78,7 @@ def _declare(lib):
         "vda_epilogue_size": ([], L),
         "vda_last_error": ([], ctypes.c_char_p),
         "vda_gemm": ([P, L, P, P, L, I, I, I, EP, P], I),
+        "vda_gemm_check": ([L, L, I, I, I, EP], I),
         "vda_conv2d": ([P, P, P, I, I, I, I, I, I, I, I, I, I, I, EP, P, L, P], I),
         "vda_conv2d_workspace": ([I, I, I, I, I, I, I, I], L),
         "vda_conv2d_res2_upsample_ok": ([I, I, I, I, I, I, I, I], I),

@@ -24,10 +24,10 @@ static long conv_im2col_bytes(int BT, int H, int W, int Cin, int ks, int stride,
   return (long)BT * Ho * Wo * ks * ks * Cin * 2;
 }
 static bool conv_takes_im2col(int BT, int H, int W, int Cin, int Cout, int ks, int stride, int pad, int up_h) {
-  if (up_h > 0 || ks != 3 || stride != 2 || Cin % 64 != 0 || Cout % 256 != 0 || g_force_tile != -1) return false;
+  if (up_h > 0 || ks != 3 || stride != 2 || Cout % 256 != 0 || g_force_tile != -1) return false;
   const long Ho = (H + 2L * pad - ks) / stride + 1, Wo = (W + 2L * pad - ks) / stride + 1;
-  const long M = (long)BT * Ho * Wo;
-  return Ho > 0 && Wo > 0 && M >= 4096 && conv_im2col_bytes(BT, H, W, Cin, ks, stride, pad) < (1L << 31);
+  // worth the copy only where the GEMM route gives the [M, 9 Cin] matrix to the phased 256x256 dense kernel
+  return Ho > 0 && Wo > 0 && vda_gemm_phased256_serves((long)BT * Ho * Wo, Cout, 9L * Cin, 9L * Cin);
 }
 
 // the halo-tiled 256-channel conv route (the only one whose epilogue reads an upsampled res2)

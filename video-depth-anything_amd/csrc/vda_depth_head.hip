@@ -11,8 +11,8 @@ extern "C" int vda_depth_head(const void* x, const void* w1, const float* b1, co
   VDA_CHECK_ARG(C % 8 == 0, "depth head needs C % 8 == 0");
   hipStream_t st = (hipStream_t)stream;
   int rc;
-  // vda_debug_force_tile(10 + cfg) (tuning build): the implicit-GEMM tail in tile configuration cfg for
-  // every shape; lower values are the GEMM's and the conv's and do not move the depth tail
+  // vda_debug_force_tile(13) (tuning build; any value >= 10): the implicit-GEMM tail for every shape; lower
+  // values are the GEMM's and the conv's and do not move the depth tail
   const bool gemm_tail = g_force_tile >= 10;
   // 1) the depth conv of vda_dconv.hip (two 4-wave blocks per CU, 64 pixels x all 64 hi/lo rows per wave)
   //    with the bilinear resize fused into its patch building: the resized map is never written
@@ -38,7 +38,7 @@ extern "C" int vda_depth_head(const void* x, const void* w1, const float* b1, co
   p.M = BT * Ho * Wo; p.N = 64; p.K = 9 * C; p.ldy = 1;
   p.epi = vda_default_epi();
   p.epi.bias = b1; p.epi.gamma = w2; p.epi.rowbias = b2;
-  return vda_launch_depth_gemm(p, g_force_tile >= 10 ? g_force_tile - 10 : 3, st);
+  return vda_launch_depth_gemm(p, st);
 }
 
 extern "C" int64_t vda_depth_head_workspace(int32_t BT, int32_t Hin, int32_t Win, int32_t C, int32_t Ho, int32_t Wo) {

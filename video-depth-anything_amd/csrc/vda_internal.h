@@ -21,13 +21,17 @@ struct GemmParams {
 VDA_KNOB_DECL(int, g_force_tile, -1);
 vda_epilogue vda_default_epi();
 int vda_check_epi(const vda_epilogue& e, int M, int N);
-// dense GEMM / implicit-GEMM conv: picks the tile configuration, applies p.epi (and stats_out)
+// dense GEMM / implicit-GEMM conv (activation none / ReLU): launches what the route says, applies p.epi
+// (and stats_out)
 int vda_launch_gemm(const GemmParams& p, hipStream_t st);
 int vda_launch_conv_gemm(const GemmParams& p, hipStream_t st);
+// the sizes the phased 256x256 dense kernel serves: X [M, K] of row stride ldx, W [N, K] (the route's own
+// term, for a caller that builds X for that kernel)
+bool vda_gemm_phased256_serves(long M, long N, long K, long ldx);
 // implicit-GEMM conv whose loader resizes its input bilinearly (p.up_h / p.up_w), register-staged
 int vda_launch_conv_reg(const GemmParams& p, hipStream_t st);
-// implicit-GEMM depth tail (3x3 C -> 32 hi/lo rows, ReLU, 1x1, ReLU; fp32 depth) in tile configuration cfg
-int vda_launch_depth_gemm(const GemmParams& p, int cfg, hipStream_t st);
+// implicit-GEMM depth tail (3x3 C -> 32 hi/lo rows, ReLU, 1x1, ReLU; fp32 depth), 256x64 tiles
+int vda_launch_depth_gemm(const GemmParams& p, hipStream_t st);
 
 // ---- vda_oc1.hip: halo-tiled 3x3 conv, Cout = 128 (output_conv1), plain and with the resize fused ----
 int vda_conv_halo(const void* x, const void* w, void* y, const float* bias, int relu, int BT, int H, int W, int Cin,

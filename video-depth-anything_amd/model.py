@@ -420,8 +420,9 @@ class VideoDepthAnything(nn.Module):
                 # temporal attention kernel instead (motion_module.py:290-293).
                 a.pe_bias = (_f(ab.pos_encoder.pe[0].float() @ wqkv.t()).to(dev)  # [max_len, 3C]
                              if ab.pos_encoder is not None else None)
-                # the LayerNorm folded into that GEMM (fp16, 'ape'; the forward takes it when a frame
-                # spans >= 256 rows): W' = gamma (.) W, colsum of the fp16 W', b' = W beta
+                # the LayerNorm folded into that GEMM (fp16, 'ape'; the forward takes it where _qkv_fold
+                # says the library serves the shape; packed only for the N % 256 == 0 that needs):
+                # W' = gamma (.) W, colsum of the fp16 W', b' = W beta
                 a.fold = not fp32 and bool(self.fold_layernorms) and a.pe_bias is not None and (3 * Cm) % 256 == 0
                 if a.fold:
                     a.qkv_wg = (wqkv * nrm.weight.detach().float()[None, :]).half().contiguous().to(dev)
@@ -482,15 +483,23 @@ class VideoDepthAnything(nn.Module):
         self._token_bias(P, int(size[0]), int(size[1]), torch.device(device))
 
     # -- forward ---------------------------------------------------------------------------
+    def _qkv_fold(self, q: _Packed, M: int, S: int, T: int) -> List[bool]:
+        """Per attention block of a motion module on M rows in frames of S: whether its LayerNorm goes into
+        the q/k/v GEMM (packed for it, and the library serves the LN fold with the per-frame row bias for
+        this shape, vda.h ln_stats); otherwise LayerNorm + GEMM."""
+        ok = any(a.fold for a in q.attn) and ops.gemm_accepts(M, 3 * q.C, q.C, ln_fold=True, ln_parts=(q.C + 255) // 256,
+                                                              rowbias=True, rdiv=S, rmod=T)
+        return [bool(a.fold and ok) for a in q.attn]
+
     def _temporal(self, q: _Packed, x: torch.Tensor, B: int, T: int, S: int) -> torch.Tensor:
         """TemporalModule on token-major frames x [B*T*S, C] (motion_module.py:64-133).
-        The attention blocks' LayerNorms (motion_module.py:175) are folded into their q/k/v GEMMs when
-        a frame spans >= 256 rows (each 256-row tile then sees <= 2 PE rows), and ff_norm (:182) into the
+        The attention blocks' LayerNorms (motion_module.py:175) are folded into their q/k/v GEMMs where
+        _qkv_fold says so (frames of >= 256 rows: each 256-row tile then sees <= 2 PE rows), and ff_norm (:182) into the
         GEGLU GEMM: the GEMM producing the residual stream h (proj_in, then each to_out) writes h's
         per-row partial sums."""
         C = q.C
         M = x.shape[0]
-        fold = [a.fold and S >= 256 and M >= 4096 for a in q.attn]
+        fold = self._qkv_fold(q, M, S, T)
         fffold = q.fffold and bool(self.fold_ff_norm)
         st = torch.empty(M + 1, (C + 255) // 256, 2, device=x.device) if any(fold) or fffold else None
         if self.fuse_groupnorm_linear:  # norm + proj_in as one op (motion_module.py:116-119)
@@ -618,9 +627,9 @@ class VideoDepthAnything(nn.Module):
         row-drop epilogue serves (vda.h drop_period), fp16, no readout."""
         if not (P.lnfold and bool(self.fold_tap_norm) and getattr(P, "projf", None) is not None):
             return False
-        M = BT * ntok
-        return (ntok >= 256 and M >= 4096 and P.C % 64 == 0 and M * P.C * 2 < 2 ** 31 and
-                all(w.shape[0] % 256 == 0 and w.numel() * 2 < 2 ** 31 for w, _, _ in P.projf))
+        nparts = (P.C + 255) // 256
+        return all(ops.gemm_accepts(BT * ntok, w.shape[0], P.C, ln_fold=True, ln_parts=nparts, drop_period=ntok)
+                   for w, _, _ in P.projf)
 
     def _reassemble(self, P: _Packed, enc, BT: int, ph: int, pw: int) -> List[torch.Tensor]:
         """DPT reassemble (dpt_temporal.py:55-69 == get_motion_features :101-131, dpt.py:60-90):

@@ -9,6 +9,7 @@ deliberately no CPU path: an op on a CPU tensor, or without the native libraries
 """
 from __future__ import annotations
 
+import functools
 from typing import Optional
 
 import torch
@@ -83,6 +84,24 @@ def gemm(x: Tensor, w: Tensor, *, bias=None, rowbias=None, rdiv=1, rmod=1, gamma
         ev1.record()
         _PROBE[tag].append((ev0, ev1, 2.0 * x.shape[0] * w.shape[0] * x.shape[1]))
     return out
+
+
+@functools.lru_cache(maxsize=None)
+def gemm_accepts(M: int, N: int, K: int, *, bias=True, ln_fold=False, ln_parts=0, rowbias=False, rdiv=1, rmod=1,
+                 drop_period=0, act=ACT_NONE, res=False, stats_out=False, ldx=None, ldy=None) -> bool:
+    """Whether ``gemm`` of contiguous, 16-byte aligned fp16 x [M, K] (row stride ``ldx``, default K) and
+    w [N, K] with these epilogue features is accepted: the library's own argument and route checks
+    (vda.h vda_gemm_check), no launch.  ``bias`` / ``ln_fold`` / ``rowbias`` / ``res`` / ``stats_out`` say
+    which tensors the call would pass.  For callers that choose between a fused epilogue (``drop_period``,
+    LN fold + ``rowbias``) and separate ops.  Memoised per argument tuple: a steady-state forward asks the
+    library nothing."""
+    ptr = lambda on: 0x1000 if on else None  # noqa: E731  (only null-ness and alignment are looked at)
+    ny = N // 2 if act == ACT_GEGLU else N
+    e = _lib.Epilogue(bias=ptr(bias), rowbias=ptr(rowbias), rdiv=int(rdiv), rmod=int(rmod), res=ptr(res), ldres=ny,
+                      act=int(act), ln_stats=ptr(ln_fold), ln_colsum=ptr(ln_fold), ln_parts=int(ln_parts),
+                      stats_out=ptr(stats_out), drop_period=int(drop_period))
+    return _lib.lib().vda_gemm_check(int(K if ldx is None else ldx), int(ny if ldy is None else ldy), int(M), int(N),
+                                     int(K), e) == 0
 
 
 _SCHED = {}
