@@ -1,10 +1,13 @@
 """In-process A/B of the attention kernels across libvda builds (tuning tool, not product code).
 
-usage: python tools/ab_attn.py [spatial|temporal|bits] LIB_A.so [LIB_B.so ...] [--rounds R]
+usage: python tools/ab_attn.py [spatial|temporal|bits] LIB_A.so [LIB_B.so ...] [--rounds R] [--calls C]
 Every case goes through the C ABI on the current torch stream; outputs are compared bit-for-bit against
 the first library's; timing rounds alternate the libraries (median / min / max us per call over the rounds).
+--calls C: calls per timed window (default: 10, temporal 20).  A 10-call window is a few ms, which times the clock
+ramp as much as the kernel; with --calls every library also runs C untimed calls of the case first, so a few
+hundred give windows of ~0.1 s at the clock the kernel holds under its own load.
   spatial   ViT-L clip shape (32 frames x 1370 tokens x 16 heads x 64), also against torch SDPA in fp32
-            (first 2 frames)
+            (first 2 frames), and the 518 x 924 shape (N = 2443)
   temporal  the four motion-module shapes (T = 32, H = 8, C in {1024, 256}), rope_theta 0 and 10000
   bits      no timing: the small shapes of tests/test_gpu_fp16_edges.py (spatial N x H and the three ramps,
             temporal (D, H) x T x S = 3, RoPE off and on) and the shapes above
@@ -28,11 +31,14 @@ SMALL_TEMPORAL = [(32, 4), (64, 4), (128, 4), (8, 3), (24, 3), (48, 3), (120, 3)
 args = sys.argv[1:]
 mode = args.pop(0) if args and args[0] in ("spatial", "temporal", "bits") else "spatial"
 rounds = 7
+calls = 0
 libs = []
 i = 0
 while i < len(args):
     if args[i] == "--rounds":
         rounds = int(args[i + 1]); i += 2
+    elif args[i] == "--calls":
+        calls = int(args[i + 1]); i += 2
     else:
         libs.append(args[i]); i += 1
 L = []
@@ -67,6 +73,12 @@ def run(name, case, timed, n=10):
     same = [bool(torch.equal(outs[0], o)) for o in outs[1:]]
     finite = bool(torch.isfinite(outs[0]).all())
     if timed:
+        if calls:
+            n = calls
+            for li, l in enumerate(L):
+                for _ in range(n):
+                    call(l, outs[li])
+            torch.cuda.synchronize()
         times = [[] for _ in L]
         for r in range(rounds):
             for li, l in enumerate(L):
@@ -93,6 +105,11 @@ if mode in ("spatial", "bits"):
     q, k, v = qkv.view(B, N, 3, H, 64)[:2].float().permute(2, 0, 3, 1, 4)
     ref = F.scaled_dot_product_attention(q, k, v).transpose(1, 2).reshape(2 * N, H * 64)
     print("rel-L1 vs SDPA:", ["%.2e" % float((o[:2 * N].float() - ref).abs().sum() / ref.abs().sum()) for o in outs], flush=True)
+if mode == "spatial":
+    B, N, H = 32, 2443, 16
+    torch.manual_seed(1)
+    qkv = (torch.randn(B * N, 3 * H * 64, device="cuda") * 1.5).half()
+    ok &= run(f"spatial 518x924 {B}x{N}x{H}x64", spatial(qkv, B, N, H), True)[1]
 if mode in ("temporal", "bits"):
     for name, S, C in MODEL_TEMPORAL:
         for rope in (0.0, 10000.0):
@@ -101,7 +118,7 @@ if mode in ("temporal", "bits"):
             ok &= run(f"temporal {name} rope={rope:g}", temporal(qkv, 1, 32, S, 8, C // 8, rope), mode == "temporal", n=20)[1]
 if mode == "bits":
     import fp16_bounds as fb
-    for N in (1, 31, 32, 33, 63, 64, 65, 127, 128, 129, 257):
+    for N in (1, 31, 32, 33, 63, 64, 65, 96, 127, 128, 129, 160, 161, 200, 257):
         for H in (1, 3):
             qkv = fb.rnd16(2 * N, 3 * H * 64, seed=N + H).to("cuda", torch.float16)
             ok &= run(f"spatial N={N} H={H}", spatial(qkv, 2, N, H), False)[1]

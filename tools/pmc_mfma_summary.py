@@ -28,7 +28,7 @@ TAGS = [
     (r"^gemm256_kernel<2, 2, false, 0, true\b", "gemm_rowbias"),
     (r"^gemm256_kernel<2, 2, false, 2\b", "gemm_geglu"),
     (r"^gemm256_kernel<2, 2, true\b", "conv_phased"),
-    (r"spatial_attn32_kernel", "spatial_attention"),
+    (r"spatial_attn(16|32)_kernel", "spatial_attention"),  # 32: the trees before the 16x16x32 kernel
     (r"temporal_attn_lds_kernel", "temporal_attention"),
     (r"depth_conv_kernel", "depth_conv"),
     (r"halo_conv_kernel", "output_conv1"),

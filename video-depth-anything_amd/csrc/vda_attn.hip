@@ -19,49 +19,77 @@ extern "C" int vda_debug_attn_clock_stamps(void* host) {
 namespace {
 
 // =============================================================================================
-// Spatial attention, D = 64, v_mfma_f32_32x32x16_f16 (the 32-cycle MFMA leaves 24 issue cycles per
-// gap for the softmax VALU, the 16x16x32 one only 8).  Block = 4 waves x 32 queries of one (batch,
-// head); a wave owns 32 query columns, a lane q = lane & 31 and half hf = lane >> 5.
-//   Sᵀ[key][q] = K·Qᵀ   A = K rows (LDS, ds_read_b128), B = Q (registers, pre-scaled by scale·log2e);
-//                       the chain starts from C = -m (a 16-register tile of the running reference
-//                       m, see the deferred re-base below), so the scores come out relative to it
-//                       with no VALU subtraction.
-//   Oᵀ += Vᵀ·Pᵀ         B = P straight from the Sᵀ registers (k order 16st + 8(j>>2) + 4hf + (j&3)),
-//                       A = Vᵀ by ds_read_b64_tr_b16 in the same permuted key order.
+// Spatial attention, D = 64, v_mfma_f32_16x16x32_f16.  Block = 4 waves x 32 queries of one (batch,
+// head); a wave owns two 16-query tiles qt, a lane query li = lane & 15 of each (qt adds 16) and the
+// key / channel group g = lane >> 4.
+//   Sᵀ[key][q] = K·Qᵀ   2 key tiles k2 x 2 query tiles x 2 K = 32 steps ks per 32-key half.  A = K row
+//                       16 k2 + li, 16-byte chunk 4 ks + g (LDS, ds_read_b128), B = Q of query 16 qt + li
+//                       (registers, pre-scaled by scale·log2e).  A chain starts from C = -m (4 registers of
+//                       the query tile's running reference m, see the deferred re-base below), so the
+//                       scores come out relative to it with no VALU subtraction.  Register r of tile
+//                       (k2, qt) holds key 16 k2 + 4g + r.
+//   Oᵀ += Vᵀ·Pᵀ         4 channel tiles ct x 2 query tiles, one K = 32 step per half.  B = P converted in
+//                       place: {tile (0, qt), tile (1, qt)} is the lane's operand (k = 8g + j is key 4g + j
+//                       for j < 4 and 16 + 4g + j - 4 above), no cross-lane move; A = Vᵀ in the same
+//                       permuted key order by two ds_read_b64_tr_b16 (rows 4g + q4 and 16 below).  Register
+//                       r of tile (ct, qt) holds channel 16 ct + 4g + r.
+// Row state (m, the row sum, the re-base test) is per query tile; a lane's row sum covers its 8 keys of
+// every half and is reduced across the four groups g once, in the epilogue.
 // K/V tiles (64 keys x 64 channels, 8 KiB each) arrive by LDS-DMA (4 x 1-KiB pieces per wave per
 // tile, keys >= N read as zeros) into a 2-slot ring, one barrier per tile.  The softmax unit is a
-// 32-key half of the tile: its 4 QK MFMAs, 16 exponentials and 4 PV MFMAs, so only half a tile of
-// scores / P is live: 119 VGPRs, FOUR waves per SIMD (4 blocks x 32 KiB of LDS per CU), which cover
+// 32-key half of the tile: its 8 QK MFMAs, 16 exponentials and 8 PV MFMAs, so only half a tile of
+// scores / P is live: 120 VGPRs, FOUR waves per SIMD (4 blocks x 32 KiB of LDS per CU), which cover
 // each other's LDS / MFMA / exp latency chains better than three waves of whole-tile work (152 VGPRs).
+// Work the result does not need is left out: a wave whose 32 queries are all >= N (the last query
+// block) only moves its DMA pieces and takes the barriers, and a half of the masked tail tile whose
+// 32 keys are all >= N is skipped whole (it would add 0 to the row sum and 0 x 0 to O): 4.5 % of the
+// wave x half units at N = 1370, 5.0 % at N = 2443.
 // The two ring slots are two __shared__ objects and the tile loop is unrolled by 2 with static slots:
 // with one ring array hipcc cannot prove that a tile's V reads do not alias the DMA in flight into the
 // other slot and drains it (s_waitcnt vmcnt(0)) before every tile's first V read.  s_setprio 1 around
 // the MFMA clusters lets a wave that reaches its MFMAs issue them ahead of the other waves' softmax VALU.
 // The block -> (b, h, query block) map keeps all query blocks of one (b, h) on one XCD (K/V re-reads
 // hit that L2).  LDS images: K slot row*8 + (chunk ^ ((row >> 1) & 7)), V slot row*8 + (chunk ^
-// (((row >> 1) & 1) << 2)): conflict-free for the b128 K reads and the b64 transposed V reads.
-// Measured (tools/ab_attn.py, same box, ViT-L 32 x 1370 x 16): whole-tile softmax, 3-slot ring, three
-// waves per SIMD (round 5) 292-298 us; halves at three waves per SIMD 297; halves + 4 waves/SIMD 282-289;
-// + static slots 276; + s_setprio 272-275 (r06_ab_attn_*.log).  Rejected: 8-wave blocks (297-302),
-// row sums by v_dot2 on the packed P (+3 %), the half's K reads issued ahead of the chain (no change),
-// and a software-pipelined wave (the next half's QK chain issued under the current half's softmax,
-// 3-slot ring, 2 / 3 waves per SIMD: 343 / 330 us, bit-identical: profiles/r06_ab_attn_pipe.log).
-// Earlier rounds: QK of tile t+1 before the softmax of tile t 333 vs 292 us; two 32-query sets per
-// wave 317.8 / 307.8 vs 275.0 us (r05_ab_attn_two_sets.log).
+// (((row >> 1) & 3) << 1)): conflict-free for the b128 K reads (16 rows of one chunk per 16 lanes) and
+// the b64 transposed V reads (8 rows x 32 B per 32 lanes), checked by brute force over the lane groups.
+// MFMA shape (profiles/attn_mfma16_ab.log, same box, random data, 32 x N x 16 heads): the 32x32x16 shape
+// was chosen because its 32-cycle MFMA leaves 24 issue cycles per gap for the softmax VALU against 8
+// for the 16-cycle 16x16x32.  With four waves per SIMD the other waves fill those gaps, and the chip
+// holds a higher clock on 16x16x32.  Measured with the dead work skipped in both:
+//   shape      N = 1370, us per call (median, min-max of 9 alternating rounds)   N = 2443     in-kernel clock (its own run)
+//   parent     272.4 (271.9-273.6)   32x32x16, dead waves and halves computed     808.7        -
+//   32x32x16   266.5 (265.2-267.4)                                                786.3        1.55 GHz
+//   16x16x32   259.2 (258.8-261.1)   kept                                         769.5        1.75 GHz
+// so skipping the dead work is worth 2.2 / 2.8 % and the shape another 2.7 / 2.1 % (fewer cycles per
+// FLOP are not what it buys: at the clock each holds the 32x32x16 kernel is at 0.56 of the peak, this
+// one at 0.52); smoke() rel-L1 7.89e-4 for both 32x32x16 builds, 6.77e-4 for this one (the K = 32 steps
+// change the summation order; rel-L1 vs SDPA 4.70e-4 for all).  On top of it, the V fragments requested
+// ahead of the softmax: 257.0 -> 254.8 us (N = 2443: 761.9 -> 759.2), bit-identical; the second half's K
+// fragments requested ahead of the first half's PV MFMAs as well: no change (256.7 / 763.7), dropped.
+// This kernel against the parent on a third box: 275.5 -> 253.8 us (-7.9 %), N = 2443 824.4 -> 756.7;
+// bench.py 707.4 -> 714.0 frames/s, above the parent in each of 5 alternating pairs
+// (profiles/attn_mfma16_forward_ab.log).
+// Measured before (tools/ab_attn.py, same box, ViT-L 32 x 1370 x 16, 32x32x16): whole-tile softmax,
+// 3-slot ring, three waves per SIMD (round 5) 292-298 us; halves at three waves per SIMD 297; halves +
+// 4 waves/SIMD 282-289; + static slots 276; + s_setprio 272-275 (r06_ab_attn_*.log).  Rejected: 8-wave
+// blocks (297-302), row sums by v_dot2 on the packed P (+3 %), the half's K reads issued ahead of the
+// chain (no change), and a software-pipelined wave (the next half's QK chain issued under the current
+// half's softmax, 3-slot ring, 2 / 3 waves per SIMD: 343 / 330 us, bit-identical:
+// profiles/r06_ab_attn_pipe.log).  Earlier rounds: QK of tile t+1 before the softmax of tile t 333 vs
+// 292 us; two 32-query sets per wave 317.8 / 307.8 vs 275.0 us (r05_ab_attn_two_sets.log).
 // =============================================================================================
 constexpr int SD = 64;       // head dim
 constexpr int SA_KT = 64;    // keys per tile
 
-// Stages the spatial kernel and both temporal kernels share: a wave's lane (r32 = lane & 31,
-// hf = lane >> 5) owns query r32 in the 32x32x16 MFMA layouts.
-// One A fragment of Vᵀ: two ds_read_b64_tr_b16, the second 8 key rows below the first (P's k order
-// 8(j>>2) + 4hf + (j&3) within a 16-key slice).
+// One A fragment of Vᵀ: two ds_read_b64_tr_b16.  Spatial kernel: the second read 16 key rows below the
+// first (P's k order above).  Temporal kernels (32x32x16 layouts, lane r32 = lane & 31, hf = lane >> 5
+// owns query r32): 8 rows below (P's k order 8(j>>2) + 4hf + (j&3) within a 16-key slice).
 __device__ __forceinline__ h8 vt_frag(const h16* p0, const h16* p1) {
   const h4 v0 = lds_read_tr16(p0), v1 = lds_read_tr16(p1);
   return h8{v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
 }
-// An Oᵀ tile dt holds query r32's channels d = dt*32 + 8gq + 4hf .. + 3 in registers 4gq .. 4gq + 3:
-// the first channel of group gq, and the group normalised by inv = 1 / row sum as fp16.
+// Temporal kernels: an Oᵀ tile dt holds query r32's channels d = dt*32 + 8gq + 4hf .. + 3 in registers
+// 4gq .. 4gq + 3: the first channel of group gq, and the group normalised by inv = 1 / row sum as fp16.
 __device__ __forceinline__ int o_chan(int dt, int gq, int hf) { return dt * 32 + 8 * gq + 4 * hf; }
 __device__ __forceinline__ h4 o_group(const f16x& o, int gq, float inv) {
   h4 v;
@@ -71,8 +99,11 @@ __device__ __forceinline__ h4 o_group(const f16x& o, int gq, float inv) {
 }
 
 __device__ __forceinline__ int sa_kslot(int row, int c) { return row * 8 + (c ^ ((row >> 1) & 7)); }
-__device__ __forceinline__ int sa_vslot(int row, int c) { return row * 8 + (c ^ (((row >> 1) & 1) << 2)); }
-__global__ __launch_bounds__(256, 4) void spatial_attn32_kernel(const h16* __restrict__ qkv, h16* __restrict__ out,
+__device__ __forceinline__ int sa_vslot(int row, int c) { return row * 8 + (c ^ (((row >> 1) & 3) << 1)); }
+// max / sum over the four 16-lane groups (lanes l, l ^ 16, l ^ 32, l ^ 48)
+__device__ __forceinline__ float quad_max(float v) { float a, b; swap16_pair(v, a, b); return half_max(fmaxf(a, b)); }
+__device__ __forceinline__ float quad_sum(float v) { float a, b; swap16_pair(v, a, b); return half_sum(a + b); }
+__global__ __launch_bounds__(256, 4) void spatial_attn16_kernel(const h16* __restrict__ qkv, h16* __restrict__ out,
                                                                 int N, int H, int nqb, int nblocks, float scale_log2) {
   __shared__ __attribute__((aligned(16))) h16 sKV0[2][SA_KT * SD];  // ring slot 0: [K | V]
   __shared__ __attribute__((aligned(16))) h16 sKV1[2][SA_KT * SD];  // ring slot 1
@@ -87,18 +118,23 @@ __global__ __launch_bounds__(256, 4) void spatial_attn32_kernel(const h16* __res
   const int C = H * SD;
   const long ld = 3L * C;
   const h16* base = qkv + (long)b * N * ld + h * SD;
-  const int r32 = lane & 31, hf = lane >> 5;
-  const int q = qb * 128 + wave * 32 + r32;
+  const int li = lane & 15, g = lane >> 4, q4 = li >> 2, p4 = li & 3;
+  const int q0 = qb * 128 + wave * 32 + li;  // query of tile 0; tile 1 is q0 + 16
+  // A wave whose 32 queries are all >= N only moves its DMA pieces and takes the barriers: no Q load,
+  // QK, softmax, PV or store (wave-uniform).
+  const bool live = qb * 128 + wave * 32 < N;
 
-  h8 qf[4];
+  h8 qf[2][2];
 #pragma unroll
-  for (int ks = 0; ks < 4; ++ks) {
-    h8 t = h8{0, 0, 0, 0, 0, 0, 0, 0};
-    if (q < N) t = __builtin_bit_cast(h8, ldg16(base + (long)q * ld + ks * 16 + hf * 8));
+  for (int qt = 0; qt < 2; ++qt)
 #pragma unroll
-    for (int e = 0; e < 8; ++e) t[e] = (h16)((float)t[e] * scale_log2);
-    qf[ks] = t;
-  }
+    for (int ks = 0; ks < 2; ++ks) {
+      h8 t = h8{0, 0, 0, 0, 0, 0, 0, 0};
+      if (q0 + 16 * qt < N) t = __builtin_bit_cast(h8, ldg16(base + (long)(q0 + 16 * qt) * ld + ks * 32 + g * 8));
+#pragma unroll
+      for (int e = 0; e < 8; ++e) t[e] = (h16)((float)t[e] * scale_log2);
+      qf[qt][ks] = t;
+    }
 
   // 16 pieces per tile (8 K + 8 V, 8 key rows each); wave w moves pieces 4w .. 4w+3.  Buffer loads
   // with the (b, h) rows as the record range: keys >= N read as zeros.  Per-lane offsets are fixed
@@ -109,7 +145,7 @@ __global__ __launch_bounds__(256, 4) void spatial_attn32_kernel(const h16* __res
   for (int j = 0; j < 4; ++j) {
     const int gp = wave * 4 + j, isv = gp >> 3, pc = gp & 7;
     const int slot = pc * 64 + lane, row = slot >> 3, pos = slot & 7;
-    const int c = isv ? (pos ^ (((row >> 1) & 1) << 2)) : (pos ^ ((row >> 1) & 7));
+    const int c = isv ? (pos ^ (((row >> 1) & 3) << 1)) : (pos ^ ((row >> 1) & 7));
     voff[j] = (unsigned)(((long)row * ld + (isv ? 2 * C : C) + c * 8) * 2);
   }
   using S0 = std::integral_constant<int, 0>;
@@ -128,22 +164,22 @@ __global__ __launch_bounds__(256, 4) void spatial_attn32_kernel(const h16* __res
     }
   };
 
-  f16x o[2] = {f16x{}, f16x{}};
-  f16x negm = {};
-  float mrun = 0.f, lsum = 0.f;
-  const int grp = lane >> 4, li = lane & 15, q4 = li >> 2, p4 = li & 3;
+  f4 o[4][2];
+#pragma unroll
+  for (int ct = 0; ct < 4; ++ct) o[ct][0] = o[ct][1] = f4{0.f, 0.f, 0.f, 0.f};
+  f4 negm[2] = {f4{0.f, 0.f, 0.f, 0.f}, f4{0.f, 0.f, 0.f, 0.f}};
+  float mrun[2] = {0.f, 0.f}, lsum[2] = {0.f, 0.f};
 
-  // Lane-constant LDS byte offsets: K fragment ks of key row r32 (key block kb adds 32 rows = 4 KiB),
-  // transposed-V read base of output tile dt (key slice ps adds 16 rows = 2 KiB, the second read of
-  // a fragment 8 rows = 1 KiB).  The swizzle terms depend on the lane only, so the reads cost one
-  // address add per ks / dt and the rest are immediate offsets.
-  unsigned kofs[4], vofs[2];
+  // Lane-constant LDS byte offsets: K fragment ks of key row li (key tile k2 adds 16 rows = 2 KiB, key
+  // block kb 32 rows = 4 KiB); transposed-V read base of channel tile ct (the second read of a fragment
+  // adds 16 rows = 2 KiB; the swizzle terms repeat every 16 / 8 rows).
+  unsigned kofs[2], vofs[4];
 #pragma unroll
-  for (int ks = 0; ks < 4; ++ks) kofs[ks] = (unsigned)sa_kslot(r32, ks * 2 + hf) * 16u;
+  for (int ks = 0; ks < 2; ++ks) kofs[ks] = (unsigned)sa_kslot(li, ks * 4 + g) * 16u;
 #pragma unroll
-  for (int dt = 0; dt < 2; ++dt) {
-    const int col = dt * 32 + (grp & 1) * 16 + 4 * p4, r0 = 4 * (grp >> 1) + q4;
-    vofs[dt] = (unsigned)(sa_vslot(r0, col >> 3) * 8 + (col & 7)) * 2u;
+  for (int ct = 0; ct < 4; ++ct) {
+    const int col = ct * 16 + 4 * p4, r0 = 4 * g + q4;
+    vofs[ct] = (unsigned)(sa_vslot(r0, col >> 3) * 8 + (col & 7)) * 2u;
   }
   // Deferred re-base (FA-style online softmax without a per-tile max): P = exp2(S - m) against the
   // running reference m; a half only re-bases when a lane's P sum passes 2^15 (then some P may not fit
@@ -153,74 +189,97 @@ __global__ __launch_bounds__(256, 4) void spatial_attn32_kernel(const h16* __res
   auto tile = [&](int kt, auto first_tag, auto mask_tag, auto sl) {
     constexpr bool FIRST = decltype(first_tag)::value;
     constexpr bool MASK = decltype(mask_tag)::value;
+    if (!live) return;
     const char* kbase = reinterpret_cast<const char*>(slot_ptr(sl, 0));
     const char* vbase = reinterpret_cast<const char*>(slot_ptr(sl, 1));
 #pragma unroll
     for (int kb = 0; kb < 2; ++kb) {
-      f16x s1;
+      // A half of the tail tile whose 32 keys are all >= N (scalar; only kb == 1 can meet it, the tile's
+      // first key is real) would add tt = 0 to lsum and 0 x 0 to o: skipped whole.
+      if (MASK && kt * SA_KT + kb * 32 >= N) continue;
+      f4 s1[2][2];  // [key tile][query tile]
       auto qk = [&]() {
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-          const h8 kf = *reinterpret_cast<const h8*>(kbase + kofs[ks] + kb * 4096);
-          s1 = mfma32(kf, qf[ks], ks == 0 ? negm : s1);
-        }
+        for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+          for (int k2 = 0; k2 < 2; ++k2) {
+            const h8 kf = *reinterpret_cast<const h8*>(kbase + kofs[ks] + kb * 4096 + k2 * 2048);
+#pragma unroll
+            for (int qt = 0; qt < 2; ++qt) s1[k2][qt] = mfma16(kf, qf[qt][ks], ks == 0 ? negm[qt] : s1[k2][qt]);
+          }
         if constexpr (MASK) {
 #pragma unroll
-          for (int r = 0; r < 16; ++r)
-            if (kt * SA_KT + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hf >= N) s1[r] = -INFINITY;
+          for (int k2 = 0; k2 < 2; ++k2)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              if (kt * SA_KT + kb * 32 + 16 * k2 + 4 * g + r >= N) s1[k2][0][r] = s1[k2][1][r] = -INFINITY;
         }
       };
-      auto smax = [&]() {
-        float mx = fmaxf(fmaxf(s1[0], s1[1]), s1[2]);
-#pragma unroll
-        for (int r = 3; r < 15; r += 2) mx = fmaxf(fmaxf(mx, s1[r]), s1[r + 1]);
-        mx = fmaxf(mx, s1[15]);
-        return half_max(mx);
+      auto smax = [&](int qt) {
+        const f4 a = s1[0][qt], c = s1[1][qt];
+        float mx = fmaxf(fmaxf(a[0], a[1]), a[2]);
+        mx = fmaxf(fmaxf(mx, a[3]), c[0]);
+        mx = fmaxf(fmaxf(mx, c[1]), c[2]);
+        return quad_max(fmaxf(mx, c[3]));
       };
-      auto rebase = [&](float sh) {
-        mrun += sh;
+      auto rebase = [&](int qt, float sh) {
+        mrun[qt] += sh;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) negm[r] = -mrun;
-        s1 -= sh;
+        for (int r = 0; r < 4; ++r) negm[qt][r] = -mrun[qt];
+        s1[0][qt] -= sh;
+        s1[1][qt] -= sh;
       };
       h8 pf[2];
-      float tt;
+      float tt[2];
       auto expo = [&]() {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float pv = __builtin_amdgcn_exp2f(s1[r]);
-          tt = r == 0 ? pv : tt + pv;  // (no add of 0 to start the chain)
-          pf[r >> 3][r & 7] = (h16)pv;
-        }
+        for (int qt = 0; qt < 2; ++qt)
+#pragma unroll
+          for (int r = 0; r < 8; ++r) {
+            const float pv = __builtin_amdgcn_exp2f(s1[r >> 2][qt][r & 3]);
+            tt[qt] = r == 0 ? pv : tt[qt] + pv;
+            pf[qt][r] = (h16)pv;
+          }
       };
       __builtin_amdgcn_s_setprio(1);
       qk();
       __builtin_amdgcn_s_setprio(0);
+      // the half's four Vᵀ fragments requested here, so their LDS latency passes under the softmax VALU
+      // (left to the scheduler they are issued in front of the PV MFMAs that wait for them)
+      h8 vf[4];
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct) {
+        const h16* va = reinterpret_cast<const h16*>(vbase + vofs[ct] + kb * 4096);
+        vf[ct] = vt_frag(va, va + 16 * SD);
+      }
+      __builtin_amdgcn_sched_barrier(0);
       if (FIRST && kb == 0) {
-        rebase(smax());
+        rebase(0, smax(0));
+        rebase(1, smax(1));
         expo();
       } else {
         expo();
-        if (__any(!(tt <= 32768.f))) {  // rare: re-base this half on its true max and redo it
+        if (__any(!(fmaxf(tt[0], tt[1]) <= 32768.f))) {  // rare: re-base this half on its true max and redo it
           qk();  // the scores again (the K slot is still resident): they need not stay live past expo
-          const float sh = fmaxf(smax(), 0.f);
-          const float alpha = __builtin_amdgcn_exp2f(-sh);
-          lsum *= alpha;
-          o[0] *= alpha;
-          o[1] *= alpha;
-          rebase(sh);
+#pragma unroll
+          for (int qt = 0; qt < 2; ++qt) {
+            const float sh = fmaxf(smax(qt), 0.f);
+            const float alpha = __builtin_amdgcn_exp2f(-sh);
+            lsum[qt] *= alpha;
+#pragma unroll
+            for (int ct = 0; ct < 4; ++ct) o[ct][qt] *= alpha;
+            rebase(qt, sh);
+          }
           expo();
         }
       }
-      lsum += tt;
+      lsum[0] += tt[0];
+      lsum[1] += tt[1];
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-      for (int ps = 0; ps < 2; ++ps) {  // the two output tiles' chains interleaved
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt) {
-          const h16* va = reinterpret_cast<const h16*>(vbase + vofs[dt] + (kb * 2 + ps) * 2048);
-          o[dt] = mfma32(vt_frag(va, va + 8 * SD), pf[ps], o[dt]);
-        }
+      for (int ct = 0; ct < 4; ++ct) {  // 8 independent MFMAs, a V fragment feeds both query tiles
+        o[ct][0] = mfma16(vf[ct], pf[0], o[ct][0]);
+        o[ct][1] = mfma16(vf[ct], pf[1], o[ct][1]);
       }
       __builtin_amdgcn_s_setprio(0);
     }
@@ -231,6 +290,7 @@ __global__ __launch_bounds__(256, 4) void spatial_attn32_kernel(const h16* __res
   auto enter = [&](int kt, auto next_slot) {
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), as the builtin: hipcc's own wait bookkeeping sees it
     __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");  // compiler-only: no LDS read of tile kt moves above the barrier
     if (kt + 1 < ntiles) dma(kt + 1, next_slot);
   };
   // a tile whose slot is only known at run time (the first, an odd leftover and the partial last one)
@@ -252,14 +312,23 @@ __global__ __launch_bounds__(256, 4) void spatial_attn32_kernel(const h16* __res
   }
   if (kt < nfull) tile_any(kt, std::false_type{}, std::false_type{});
   if (tail && ntiles > 1) tile_any(ntiles - 1, std::false_type{}, std::true_type{});
-  // epilogue: channels o_chan(dt, gq, hf), added to op term by term (the constants become store offsets)
-  const float inv = 1.f / half_sum(lsum);
-  if (q < N) {
-    h16* op = out + ((long)b * N + q) * C + h * SD;
+  // epilogue: the row sums across the four key groups, then channels 16 ct + 4g .. + 3 of each query
+  if (live) {
 #pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
+    for (int qt = 0; qt < 2; ++qt) {
+      const float inv = 1.f / quad_sum(lsum[qt]);
+      const int q = q0 + 16 * qt;
+      if (q < N) {
+        h16* op = out + ((long)b * N + q) * C + h * SD + 4 * g;
 #pragma unroll
-      for (int gq = 0; gq < 4; ++gq) *reinterpret_cast<h4*>(op + dt * 32 + 8 * gq + 4 * hf) = o_group(o[dt], gq, inv);
+        for (int ct = 0; ct < 4; ++ct) {
+          h4 v;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) v[r] = (h16)(o[ct][qt][r] * inv);
+          *reinterpret_cast<h4*>(op + ct * 16) = v;
+        }
+      }
+    }
   }
   ATSC(1);
 }
@@ -520,7 +589,7 @@ extern "C" int vda_spatial_attention(const void* qkv, void* out, int32_t B, int3
   const int nqb = (N + 127) / 128;
   const long nb = (long)nqb * H * B;
   VDA_CHECK_ARG(nb < 0x7fffffffL, "attention grid too large");
-  hipLaunchKernelGGL(spatial_attn32_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, (const h16*)qkv,
+  hipLaunchKernelGGL(spatial_attn16_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, (const h16*)qkv,
                      (h16*)out, N, H, nqb, (int)nb, scale * 1.4426950408889634f);
   VDA_LAUNCH_CHECK();
   return 0;
