@@ -752,7 +752,9 @@ class VideoDepthAnything(nn.Module):
             if pidx and not all(-o1.shape[0] <= i < o1.shape[0] for i in pidx):
                 bad = next(i for i in pidx if not -o1.shape[0] <= i < o1.shape[0])
                 raise IndexError(f"index {bad} is out of bounds for dimension 0 with size {o1.shape[0]}")
-            it = torch.tensor(pidx, dtype=torch.long, device=x.device)
+            # a negative index counts from the end of what it indexes: the T - 1 context frames here, the T
+            # frames of path_3 below (index_select itself takes no negative index)
+            it = torch.tensor([i if i >= 0 else i + o1.shape[0] for i in pidx], dtype=torch.long, device=x.device)
             l1 = torch.cat([o1.index_select(0, it), new[0]], 0)
             l2 = torch.cat([o2.index_select(0, it), new[1]], 0)
             sel = [i if i >= 0 else i + T for i in pidx] + [T - 1]  # path_3[idx] has T rows (:233)
