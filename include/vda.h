@@ -436,6 +436,36 @@ int vda_depth_colorize(const float* depth, int32_t F, int32_t H, int32_t W, cons
  *   followed by the RGB kernel.  ws: vda_preprocess_yuv_workspace(N, h, w, H, W) bytes of device memory owned
  *   by the caller, 0 when the tile route serves the shape (ws may be NULL then); it needs no initialisation.
  *   H, N <= 65535; on the workspace route also h <= 65535.
+ *
+ * vda_yuv_downscale: out uint8 [N, h2, w2, 3] (any alignment) = the RGB frames of vda_yuv_to_rgb resized as
+ *   Pillow's Image.resize((w2, h2), Image.BICUBIC) resizes an 8-bit image (what read_video_frames does for
+ *   --max_res), bit for bit.  That resampler is separable and runs in integer fixed point; per axis, for input
+ *   size `in` and output size `out`, in IEEE doubles with one rounding per operation:
+ *     scale = in / out;  fs = max(scale, 1);  support = 2 * fs;  ksize = (int)ceil(support) * 2 + 1
+ *     for xx < out:  center = (xx + 0.5) * scale
+ *       xmin = max((int)(center - support + 0.5), 0);  n = min((int)(center + support + 0.5), in) - xmin
+ *       w[x] = bicubic((x + xmin - center + 0.5) * (1 / fs)) for x < n, summed in that order into ww; w[x] /= ww
+ *       k[xx][x] = (int)(w[x] * 2^22 + (w[x] < 0 ? -0.5 : 0.5));  k[xx][n ..] = 0;  bounds[xx] = (xmin, n)
+ *     bicubic(x), a = -0.5:  |x| < 1: ((a + 2)|x| - (a + 3)) x^2 + 1;  |x| < 2: (((|x| - 5)|x| + 8)|x| - 4) a;  else 0
+ *     pixel = clamp((2^21 + sum_x src[xmin + x] * k[xx][x]) >> 22, 0, 255)      (int32, arithmetic shift)
+ *   The horizontal pass runs first over the three channels and is rounded to uint8, then the vertical pass; a
+ *   pass whose size does not change (w2 == w, h2 == h) copies, and its tables are not read (they may be NULL).
+ *   An axis may also grow (ensure_even adds a pixel): the tables carry it.
+ *   vda_resample_taps(in, out) = ksize and vda_resample_tables fill k [out, ksize] and bounds [out, 2] on the
+ *   HOST: pure functions, no device, no allocation, no state.  vda_yuv_downscale takes the tables of the two
+ *   axes in DEVICE memory: kx [w2, vda_resample_taps(w, w2)], bx [w2, 2], ky [h2, vda_resample_taps(h, h2)],
+ *   by [h2, 2], int32, 4-byte aligned.  Table entries are clamped to the staged footprint, so wrong tables
+ *   give wrong pixels, never an access outside src or out.  The kernel multiplies with 24-bit multiplies: a
+ *   coefficient must lie in [-2^23, 2^23), as every coefficient of vda_resample_tables does (a row's positive
+ *   coefficients sum to at most 1.13 * 2^22 over every ratio from 5 -> 6 to 10240 -> 1280).
+ *   One route: a workgroup owns 64 x 16 output pixels of a frame, converts the source rows it needs 8 at a time
+ *   into LDS, filters them horizontally into LDS as uint8, filters that vertically and stores each row of the
+ *   tile as a bytewise head, dwords and a bytewise tail.  Neither the RGB frame nor the intermediate is written
+ *   to memory; vda_yuv_downscale_workspace is 0 for every shape and ws may be NULL.
+ *   Compiled cap: at most 29 coefficients per axis (a ratio in / out up to 7, e.g. 8960 -> 1280) and at most
+ *   64 KiB of LDS for the tile.  vda_yuv_downscale_ok(h, w, h2, w2) is 1 when the kernel serves the shape;
+ *   otherwise vda_yuv_downscale returns -22 without launching (callers then resize on the host).
+ *   h2, N <= 65535.
  */
 enum {
   VDA_YUV_420 = 0,
@@ -449,6 +479,13 @@ int64_t vda_preprocess_yuv_workspace(int32_t N, int32_t h, int32_t w, int32_t H,
 int vda_preprocess_yuv(const uint8_t* src, int32_t N, int32_t h, int32_t w, int64_t frame_stride, int32_t chroma,
                        float* out, int32_t H, int32_t W, const float* mean, const float* stdv, void* ws,
                        int64_t ws_bytes, void* stream);
+int32_t vda_resample_taps(int32_t in, int32_t out);
+int vda_resample_tables(int32_t in, int32_t out, int32_t* k, int32_t* bounds);
+int vda_yuv_downscale_ok(int32_t h, int32_t w, int32_t h2, int32_t w2);
+int64_t vda_yuv_downscale_workspace(int32_t N, int32_t h, int32_t w, int32_t h2, int32_t w2);
+int vda_yuv_downscale(const uint8_t* src, int32_t N, int32_t h, int32_t w, int64_t frame_stride, int32_t chroma,
+                      const int32_t* kx, const int32_t* bx, const int32_t* ky, const int32_t* by, uint8_t* out,
+                      int32_t h2, int32_t w2, void* ws, int64_t ws_bytes, void* stream);
 
 /*
  * fp32 mode (infer_video_depth(fp32=True) / autocast off, video_depth.py:366-368): the same ops

@@ -14,6 +14,8 @@ uses the deterministic recipe of vda_amd.weights when no checkpoint is available
 vda_depth_colorize) and writes the same file as the host path; ``--vis_chroma 420`` writes a 4:2:0 .y4m.
 ``--decode device`` (a .y4m input) indexes the file instead of decoding it: every window batch uploads the planar
 YUV bytes of its frames and vda_preprocess_yuv decodes them into the network input; the depth is the same.
+``--downscale device`` (with ``--decode device``) also makes the ``--max_res`` downscale on the device
+(vda_yuv_downscale, Pillow's antialiased bicubic in its own integer arithmetic): 1080p and 4K files take that path too.
 """
 import argparse
 import os
@@ -73,7 +75,11 @@ def add_arguments(p):
     p.add_argument("--decode", type=str, default="host", choices=["host", "device"],
                    help="where a .y4m input is decoded: on the host (numpy, the whole file up front), or on the "
                         "device, from the file's YUV bytes as each window needs them (the same depth; needs a "
-                        ".y4m input, a CUDA device and no --max_res downscale)")
+                        ".y4m input, a CUDA device and, without --downscale device, no --max_res downscale)")
+    p.add_argument("--downscale", type=str, default="host", choices=["host", "device"],
+                   help="where frames larger than --max_res are downscaled: on the host (Pillow's antialiased bicubic, "
+                        "as the reference does), or with --decode device on the device from the file's YUV bytes "
+                        "(vda_yuv_downscale: the same frames bit for bit, so the same depth)")
     return p
 
 
@@ -87,6 +93,8 @@ def parse(argv=None):
     a = p.parse_args(argv)
     if a.vis == "device" and a.stitch != "device":
         p.error("--vis device needs --stitch device (it colours the depth where the device stitcher leaves it)")
+    if a.downscale == "device" and a.decode != "device":
+        p.error("--downscale device needs --decode device (it downscales the planar YUV frames that path uploads)")
     if a.decode == "device":
         if os.path.splitext(a.input_video)[1].lower() != ".y4m":
             p.error("--decode device needs a .y4m input (it uploads the file's planar YUV frames); convert the video "
@@ -98,15 +106,18 @@ def parse(argv=None):
 
 def open_input(args):
     """The input frames and their rate: decoded on the host (``--decode host``), or with ``--decode device`` the
-    indexed .y4m file (``video_io.Y4MFrames``), which refuses a ``--max_res`` that would downscale it."""
+    indexed .y4m file (``video_io.Y4MFrames``).  A ``--max_res`` that would downscale it is refused unless
+    ``--downscale device`` asks for that step on the device: then the object carries the downscaled size."""
     from vda_amd import video_io as VIO
     if args.decode != "device":
         return VIO.read_video_frames(args.input_video, args.max_len, args.target_fps, args.max_res)
+    if args.downscale == "device":
+        return VIO.open_y4m(args.input_video, args.max_len, args.target_fps, args.max_res)
     frames, fps = VIO.open_y4m(args.input_video, args.max_len, args.target_fps)
     if args.max_res > 0 and max(frames.h, frames.w) > args.max_res:
         sys.exit(f"{args.input_video}: --decode device does not downscale ({frames.w}x{frames.h} exceeds --max_res "
                  f"{args.max_res}; the host path does that step with Pillow's antialiased bicubic): pass --max_res -1 "
-                 "or --decode host")
+                 "or --decode host, or --downscale device for the same step on the device")
     return frames, fps
 
 

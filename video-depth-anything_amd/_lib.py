@@ -31,6 +31,8 @@ EXPORTED = (
     "vda_depth_eval_workspace", "vda_depth_eval_fit", "vda_depth_eval_metrics",
     "vda_depth_range_workspace", "vda_depth_range", "vda_depth_colorize_bytes", "vda_depth_colorize",
     "vda_yuv_to_rgb", "vda_preprocess_yuv_workspace", "vda_preprocess_yuv",
+    "vda_resample_taps", "vda_resample_tables", "vda_yuv_downscale_ok", "vda_yuv_downscale_workspace",
+    "vda_yuv_downscale",
     "vda_gemm_f32", "vda_conv2d_f32", "vda_layernorm_f32", "vda_groupnorm_f32", "vda_spatial_attention_f32",
     "vda_temporal_attention_f32", "vda_upsample_bilinear_f32", "vda_patch_im2col_f32", "vda_depth_head_f32",
 )
@@ -110,6 +112,11 @@ def _declare(lib):
         "vda_yuv_to_rgb": ([P, I, I, I, L, I, P, P], I),
         "vda_preprocess_yuv_workspace": ([I, I, I, I, I], L),
         "vda_preprocess_yuv": ([P, I, I, I, L, I, P, I, I, POINTER(F), POINTER(F), P, L, P], I),
+        "vda_resample_taps": ([I, I], I),
+        "vda_resample_tables": ([I, I, P, P], I),
+        "vda_yuv_downscale_ok": ([I, I, I, I], I),
+        "vda_yuv_downscale_workspace": ([I, I, I, I, I], L),
+        "vda_yuv_downscale": ([P, I, I, I, L, I, P, P, P, P, P, I, I, P, L, P], I),
         "vda_gemm_f32": ([P, L, P, P, L, I, I, I, EP, P], I),
         "vda_conv2d_f32": ([P, P, P, I, I, I, I, I, I, I, I, I, EP, P], I),
         "vda_layernorm_f32": ([P, L, P, P, P, I, I, F, I, P], I),

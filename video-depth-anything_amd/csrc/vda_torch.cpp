@@ -722,10 +722,47 @@ Tensor preprocess_yuv(const Tensor& payload, int64_t h, int64_t w, int64_t chrom
   return out;
 }
 
+// The resampling tables of one axis (vda_resample_tables): k int32 [out, vda_resample_taps(in, out)], b int32 [out, 2].
+void need_tables(const Tensor& k, const Tensor& b, int64_t in, int64_t out, const char* axis, const Tensor& like) {
+  need_contig(k, at::kInt, axis, like);
+  need_contig(b, at::kInt, axis, like);
+  const int64_t taps = vda_resample_taps((int32_t)in, (int32_t)out);
+  TORCH_CHECK(k.dim() == 2 && k.size(0) == out && k.size(1) == taps, "vda yuv_downscale: the ", axis,
+              " coefficients must be [", out, ", ", taps, "] for ", in, " -> ", out, ", got ", k.sizes());
+  TORCH_CHECK(b.dim() == 2 && b.size(0) == out && b.size(1) == 2, "vda yuv_downscale: the ", axis,
+              " bounds must be [", out, ", 2], got ", b.sizes());
+}
+
+Tensor yuv_downscale(const Tensor& payload, int64_t h, int64_t w, int64_t chroma, int64_t h2, int64_t w2,
+                     const Tensor& kx, const Tensor& bx, const Tensor& ky, const Tensor& by) {
+  const int64_t stride = yuv_frame_stride(payload, h, w, chroma, "vda yuv_downscale");
+  TORCH_CHECK(h2 >= 1 && w2 >= 1 && w2 <= INT32_MAX, "vda yuv_downscale: h2 and w2 must be positive");
+  const int64_t N = payload.size(0);
+  TORCH_CHECK(N <= 65535 && h2 <= 65535, "vda yuv_downscale: N and h2 <= 65535 per call");
+  need_tables(kx, bx, w, w2, "horizontal", payload);
+  need_tables(ky, by, h, h2, "vertical", payload);
+  TORCH_CHECK(vda_yuv_downscale_ok((int32_t)h, (int32_t)w, (int32_t)h2, (int32_t)w2) == 1, "vda yuv_downscale: ", h, "x", w,
+              " -> ", h2, "x", w2, " is beyond the kernel's ratio (vda_yuv_downscale_ok)");
+  Tensor out = at::empty({N, h2, w2, 3}, payload.options());
+  if (payload.is_meta() || N == 0) return out;
+  const at::OptionalDeviceGuard g(payload.device());
+  const int64_t wsb = vda_yuv_downscale_workspace((int32_t)N, (int32_t)h, (int32_t)w, (int32_t)h2, (int32_t)w2);
+  Tensor ws;
+  if (wsb > 0) ws = at::empty({wsb}, payload.options());
+  check_rc(vda_yuv_downscale((const uint8_t*)payload.data_ptr(), (int32_t)N, (int32_t)h, (int32_t)w, stride,
+                             (int32_t)chroma, (const int32_t*)kx.data_ptr(), (const int32_t*)bx.data_ptr(),
+                             (const int32_t*)ky.data_ptr(), (const int32_t*)by.data_ptr(), (uint8_t*)out.data_ptr(),
+                             (int32_t)h2, (int32_t)w2, wsb > 0 ? ws.data_ptr() : nullptr, wsb, stream_of(payload)),
+           "vda_yuv_downscale");
+  return out;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(vda, m) {
   m.def("yuv_to_rgb(Tensor payload, int h, int w, int chroma) -> Tensor");
+  m.def("yuv_downscale(Tensor payload, int h, int w, int chroma, int h2, int w2, Tensor kx, Tensor bx, Tensor ky, "
+        "Tensor by) -> Tensor");
   m.def("preprocess_yuv(Tensor payload, int h, int w, int chroma, int H, int W, float[] mean, float[] std) -> Tensor");
   m.def("depth_range(Tensor depth) -> Tensor");
   m.def("depth_colorize(Tensor depth, Tensor range, Tensor? lut, int layout) -> Tensor");
@@ -785,6 +822,7 @@ TORCH_LIBRARY(vda, m) {
     m.impl("depth_colorize", &depth_colorize);                \
     m.impl("yuv_to_rgb", &yuv_to_rgb);                        \
     m.impl("preprocess_yuv", &preprocess_yuv);                \
+    m.impl("yuv_downscale", &yuv_downscale);                  \
   }
 
 VDA_IMPL(CUDA)

@@ -367,6 +367,32 @@ def yuv_to_rgb(payload: Tensor, h: int, w: int, chroma) -> Tensor:
     return _vda().yuv_to_rgb(payload, h, w, code)
 
 
+@functools.lru_cache(maxsize=None)
+def yuv_downscale_accepts(h: int, w: int, h2: int, w2: int) -> bool:
+    """Whether ``yuv_downscale`` serves h x w -> h2 x w2 (vda.h vda_yuv_downscale_ok: at most 29 coefficients
+    per axis, a ratio up to 7).  Memoised per shape."""
+    return _lib.lib().vda_yuv_downscale_ok(int(h), int(w), int(h2), int(w2)) == 1
+
+
+@functools.lru_cache(maxsize=None)
+def _downscale_tables(h: int, w: int, h2: int, w2: int, device: str):
+    """(kx, bx, ky, by) of ``decode.resample_tables`` on ``device``: built and uploaded once per shape and device."""
+    from .decode import resample_tables
+    tables = tuple(t.to(device) for t in resample_tables(w, w2) + resample_tables(h, h2))
+    torch.cuda.current_stream(device).synchronize()  # later calls may run on other streams: the upload has landed
+    return tables
+
+
+def yuv_downscale(payload: Tensor, h: int, w: int, chroma, h2: int, w2: int) -> Tensor:
+    """Planar YUV frames (as ``yuv_to_rgb`` takes them) -> RGB uint8 [N, h2, w2, 3]: the decoded frames resized as
+    Pillow's ``Image.resize((w2, h2), Image.BICUBIC)`` does (``video_io._resize_rgb``, the ``--max_res`` step),
+    bit for bit, without the full-size RGB frames in memory (vda.h vda_yuv_downscale).  Raises for a ratio
+    ``yuv_downscale_accepts`` refuses."""
+    h, w, code = _yuv_inputs(payload, h, w, chroma)
+    kx, bx, ky, by = _downscale_tables(h, w, int(h2), int(w2), str(payload.device))
+    return _vda().yuv_downscale(payload, h, w, code, int(h2), int(w2), kx, bx, ky, by)
+
+
 def preprocess_yuv(payload: Tensor, h: int, w: int, chroma, H: int, W: int, mean=(0.485, 0.456, 0.406),
                    std=(0.229, 0.224, 0.225)) -> Tensor:
     """Planar YUV frames (as ``yuv_to_rgb`` takes them) -> normalised network input [N, 3, H, W] fp32:

@@ -103,9 +103,14 @@ class DeviceIO:
     def preprocess_planar(payload: torch.Tensor, frames, size: tuple) -> torch.Tensor:
         """``preprocess`` from the planar YUV bytes of the frames (``payload`` [N, frame_stride] uint8 on the
         device, rows as ``frames``, a ``video_io.Y4MFrames``, hands them out): vda_preprocess_yuv, the bits
-        ``preprocess`` gives for the host-decoded frames."""
+        ``preprocess`` gives for the host-decoded frames.  Frames opened with a ``max_res`` that downscales them
+        go through vda_yuv_downscale first (the RGB frames ``frames.rgb()`` gives, on the device), then
+        ``preprocess``."""
         from . import ops
-        return ops.preprocess_yuv(payload, frames.h, frames.w, frames.chroma, int(size[0]), int(size[1]), MEAN, STD)
+        if (frames.out_h, frames.out_w) == (frames.h, frames.w):
+            return ops.preprocess_yuv(payload, frames.h, frames.w, frames.chroma, int(size[0]), int(size[1]), MEAN, STD)
+        rgb = ops.yuv_downscale(payload, frames.h, frames.w, frames.chroma, frames.out_h, frames.out_w)
+        return ops.preprocess_frames(rgb, int(size[0]), int(size[1]), MEAN, STD)
 
     @staticmethod
     def resize_depth(depth: torch.Tensor, size: tuple) -> torch.Tensor:
@@ -559,7 +564,8 @@ def infer_video_depth(forward: Callable[[torch.Tensor], torch.Tensor], frames, t
     """Depth for every frame of ``frames`` (uint8 [N, h, w, 3] numpy or tensor, or a ``video_io.Y4MFrames``:
     on a GPU with an ``io`` that has ``preprocess_planar`` its frames are uploaded as the planar YUV bytes of the
     file and decoded by the preprocessing kernel, otherwise they are decoded on the host first; the depth is the
-    same bit for bit).
+    same bit for bit.  Frames opened with a ``max_res`` that downscales them are downscaled on the device too,
+    unless ``ops.yuv_downscale_accepts`` refuses the ratio: then they are decoded and resized on the host).
 
     ``forward(x[B, 32, 3, H, W]) -> depth[B, 32, H, W]`` is the clip forward (the model, or any
     callable); ``prepare((H, W))``, when given, builds whatever state the forward creates lazily
@@ -589,10 +595,14 @@ def infer_video_depth(forward: Callable[[torch.Tensor], torch.Tensor], frames, t
     dev = torch.device(device)
     planar = None
     if isinstance(frames, Y4MFrames):
-        if dev.type == "cuda" and callable(getattr(io, "preprocess_planar", None)):
+        use_planar = dev.type == "cuda" and callable(getattr(io, "preprocess_planar", None))
+        if use_planar and frames.downscaled:
+            from . import ops
+            use_planar = ops.yuv_downscale_accepts(frames.h, frames.w, frames.out_h, frames.out_w)
+        if use_planar:
             planar = frames          # the window batches upload the file's YUV bytes
-        else:
-            frames = frames.rgb()    # a CPU run, or an io without the planar kernel: decode on the host
+        else:                        # a CPU run, an io without the planar kernel, or a ratio beyond the downscale
+            frames = frames.rgb()    # kernel: decode (and downscale) on the host
     if planar is None and not isinstance(frames, torch.Tensor):
         frames = torch.from_numpy(np.ascontiguousarray(frames))
     n = frames.shape[0]

@@ -11,9 +11,11 @@ and encoders that need only numpy / Pillow:
   (.mp4 ...) go through decord when it is importable.  Frame stride = max(round(source_fps / target_fps), 1); at most
   ``process_length`` frames; ``max_res`` scales the longer side down (decord branch: sizes rounded
   and made even, dc_utils.py:22-29).
-* ``open_y4m(path, process_length, target_fps) -> (Y4MFrames, fps)``: a ``.y4m`` file indexed and memory-mapped
-  but not decoded, with the same frame selection.  ``Y4MFrames.payload`` hands out the planar YUV bytes of frames
-  (what ``infer_video_depth`` uploads on a GPU, vda_amd.decode), ``rgb`` / ``np.asarray`` decode as ``read_y4m``.
+* ``open_y4m(path, process_length, target_fps, max_res=-1) -> (Y4MFrames, fps)``: a ``.y4m`` file indexed and
+  memory-mapped but not decoded, with the same frame selection.  ``Y4MFrames.payload`` hands out the planar YUV bytes
+  of frames (what ``infer_video_depth`` uploads on a GPU, vda_amd.decode), ``rgb`` / ``np.asarray`` decode as
+  ``read_y4m``; with a ``max_res`` below the longer side its RGB frames are the downscaled ones of
+  ``read_video_frames`` (on a GPU made from the same payload by vda_yuv_downscale).
 * ``save_video(frames, path, fps, is_depths, grayscale, spectral)`` (dc_utils.py:72-89): depth is
   min/max-normalised to uint8 over the whole clip and mapped through matplotlib's inferno (or
   Spectral) table; written as ``.y4m`` (4:4:4), or animated GIF / PNG / WebP via Pillow; ``.mp4``
@@ -144,9 +146,15 @@ class Y4MFrames:
     """The frames of a YUV4MPEG2 file, indexed but not decoded (``open_y4m``).  The file is memory-mapped;
     ``payload`` hands out the planar YUV bytes of frames as they lie in the file (what vda_amd.decode's
     kernels take), ``rgb`` / ``np.asarray`` decode on the host as ``read_y4m`` does, so anything that wants
-    RGB frames takes this object too.  ``shape`` is that of the RGB frames, ``(N, h, w, 3)``."""
+    RGB frames takes this object too.  ``shape`` is that of the RGB frames, ``(N, out_h, out_w, 3)``.
 
-    def __init__(self, path: str, data, offsets, w: int, h: int, cw: int, ch: int, chroma: str):
+    ``out_h`` / ``out_w`` are the file's ``h`` / ``w`` unless ``open_y4m`` was given a ``max_res`` below the
+    frame's longer side: then they are the size ``read_video_frames`` downscales to, ``rgb`` resizes the
+    decoded frames as it does (``_resize_rgb``), and ``payload`` still hands out the file's full-size planes
+    (vda_yuv_downscale makes the same RGB frames of them on the device)."""
+
+    def __init__(self, path: str, data, offsets, w: int, h: int, cw: int, ch: int, chroma: str,
+                 out_h: Optional[int] = None, out_w: Optional[int] = None):
         self.path = path
         self.data = data                              # uint8 view of the whole file
         self.offsets = np.asarray(offsets, np.int64)  # byte offset of each selected frame's payload
@@ -154,10 +162,16 @@ class Y4MFrames:
         self.chroma = chroma                          # "420", "422", "444" or "mono"
         self.payload_bytes = self.w * self.h + 2 * self.cw * self.ch
         self.frame_stride = (self.payload_bytes + 15) // 16 * 16  # frames of a payload block are padded to this
+        self.out_h = self.h if out_h is None else int(out_h)  # the size of the RGB frames (max_res)
+        self.out_w = self.w if out_w is None else int(out_w)
+
+    @property
+    def downscaled(self) -> bool:
+        return (self.out_h, self.out_w) != (self.h, self.w)
 
     @property
     def shape(self) -> tuple:
-        return (len(self.offsets), self.h, self.w, 3)
+        return (len(self.offsets), self.out_h, self.out_w, 3)
 
     def __len__(self) -> int:
         return len(self.offsets)
@@ -177,12 +191,14 @@ class Y4MFrames:
         return out
 
     def rgb(self, indices=None) -> np.ndarray:
-        """Frames ``indices`` (default: all) decoded on the host: uint8 [n, h, w, 3], equal to ``read_y4m``."""
+        """Frames ``indices`` (default: all) decoded on the host: uint8 [n, out_h, out_w, 3], equal to
+        ``read_y4m`` (then ``_resize_rgb`` when the object downscales)."""
         idx = range(len(self)) if indices is None else [int(i) for i in indices]
-        out = np.zeros((len(idx), self.h, self.w, 3), np.uint8)
+        out = np.zeros((len(idx), self.out_h, self.out_w, 3), np.uint8)
         for j, i in enumerate(idx):
             o = int(self.offsets[i])
-            out[j] = _decode_payload(self.data[o:o + self.payload_bytes], self.w, self.h, self.cw, self.ch)
+            f = _decode_payload(self.data[o:o + self.payload_bytes], self.w, self.h, self.cw, self.ch)
+            out[j] = _resize_rgb(f[None], self.out_h, self.out_w)[0] if self.downscaled else f
         return out
 
     def __array__(self, dtype=None, copy=None):
@@ -190,11 +206,13 @@ class Y4MFrames:
         return a if dtype is None else a.astype(dtype, copy=False)
 
 
-def open_y4m(path: str, process_length: int = -1, target_fps: float = -1) -> Tuple[Y4MFrames, float]:
+def open_y4m(path: str, process_length: int = -1, target_fps: float = -1, max_res: int = -1) -> Tuple[Y4MFrames, float]:
     """Index a YUV4MPEG2 file without decoding it: ``(Y4MFrames, fps)`` with ``read_video_frames``' frame
     selection (stride = max(round(source_fps / target_fps), 1), at most ``process_length`` frames).  The
     stream header is parsed and refused as ``read_y4m`` does; the FRAME headers are walked once, since they
-    may carry parameters and the payloads are therefore not a fixed stride apart."""
+    may carry parameters and the payloads are therefore not a fixed stride apart.  With ``max_res`` > 0 and
+    a longer side above it, the object's RGB frames have ``read_video_frames``' downscaled size
+    (``Y4MFrames.out_h`` / ``out_w``); the payload stays the file's."""
     import mmap
     with open(path, "rb") as f:
         mm = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
@@ -216,7 +234,11 @@ def open_y4m(path: str, process_length: int = -1, target_fps: float = -1) -> Tup
     if process_length != -1 and process_length < len(idx):
         idx = idx[:process_length]
     data = np.frombuffer(mm, np.uint8)
-    return Y4MFrames(path, data, [offsets[i] for i in idx], w, h, cw, ch, chroma), fps
+    out_h, out_w = h, w
+    if max_res > 0 and max(h, w) > max_res:
+        s = max_res / max(h, w)
+        out_h, out_w = ensure_even(round(h * s)), ensure_even(round(w * s))
+    return Y4MFrames(path, data, [offsets[i] for i in idx], w, h, cw, ch, chroma, out_h, out_w), fps
 
 
 def _subsample_420(p: np.ndarray) -> np.ndarray:
