@@ -106,6 +106,14 @@ typedef struct vda_epilogue {
    * rowbias / stats_out, N % 256 == 0, and a shape the GEMM route gives to the phased 256x256 kernel;
    * -22 otherwise (vda_gemm_check answers for a shape). */
   int32_t drop_period;
+  /* bias9 (vda_conv2d with up_h / up_w only): a [9][N] fp32 table used INSTEAD of `bias`, one row per class
+   * (top / middle / bottom row of the output map) x (left / middle / right column), row 3 r + c: the bias of a
+   * 3x3 zero-padded conv composed with a biased 1x1 conv in front of it (refinenet1's out_conv, blocks.py:160,
+   * then the x2 resize, whose weights sum to 1, then output_conv1, dpt.py:117): the 1x1 bias reaches an output
+   * pixel only through the taps the padding leaves in bounds, bias9[class] = b_1 + sum_{in-bounds t} W_1[t] b_o.
+   * Only the outermost ring of output pixels differs from the middle class.  Served by the halo conv with the
+   * fused resize alone (vda_conv2d_bias9_ok says for which shapes; -22 elsewhere).  NULL: `bias`. */
+  const float* bias9;
 } vda_epilogue;
 
 /* Version / diagnostics. */
@@ -159,6 +167,43 @@ int64_t vda_conv2d_workspace(int32_t BT, int32_t H, int32_t W, int32_t Cin, int3
  * else 0 (the caller materialises the upsample with vda_upsample_bilinear instead). */
 int vda_conv2d_res2_upsample_ok(int32_t BT, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t ks,
                                 int32_t stride, int32_t pad);
+/* 1 when the 3x3 / stride 1 / pad 1 vda_conv2d of X [BT, H, W, Cin] through the resize to (up_h, up_w) takes a
+ * 9-class bias table (vda_epilogue.bias9), else 0 (the caller keeps the 1x1 conv and the plain bias). */
+int vda_conv2d_bias9_ok(int32_t BT, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t up_h, int32_t up_w);
+
+/*
+ * Sub-pixel conv: ConvTranspose2d(kernel = stride = s, bias) followed by a zero-padded 3x3 conv (no bias),
+ * composed by the caller into one linear map of the low-resolution input (dpt.py:70-82 resize_layers[0] / [1]
+ * then blocks.py:20-32 layer1_rn / layer2_rn; nothing stands between the two in dpt_temporal.py:55-69, :71-80).
+ * X [BT, h, w, Cin] half -> Y [BT, s h, s w, Cout] half, written once; the [BT, s h, s w, Cin] map between the two
+ * convs never exists.  With Wt[a][b] the ConvT taps, Wr[dy][dx] the 3x3 weights and p = X zero outside its own
+ * frame, for a, b in [0, s):
+ *   Y[s i + a, s j + b] = sum_{di, dj in {-1, 0, 1}} Wc[a][b][di][dj] p[i + di, j + dj] + bias9[class(y, x)]
+ *   Wc[a][b][di][dj] = sum over (dy, dx) with floor((a + dy) / s) = di, floor((b + dx) / s) = dj of
+ *                      Wr[dy][dx] Wt[(a + dy) mod s][(b + dx) mod s]^T                        ([Cout, Cin])
+ * Phase a = 0 uses di in {-1, 0}, a = s - 1 uses {0, +1}, the phases between use di = 0 only (columns alike), so
+ * a phase sees a 1x1, 1x2, 2x1 or 2x2 window.  The phases are served in groups of four of one window shape; `w`
+ * holds the groups one after the other, each [4 * Cout, K] half (K contiguous), rows (phase in the order listed,
+ * co), K = the window's source pixels (in the order listed, as (di, dj) relative to the phase's own (i, j)) x Cin:
+ *   s = 2: one group, phases (0,0) (0,1) (1,0) (1,1), window pixels (ci-1, cj-1) (ci, cj-1) (ci, cj) (ci-1, cj)
+ *          of corner ci = i + a, cj = j + b, i.e. (di, dj) = (r + a, c + b) for corner-relative (r, c) in
+ *          (-1,-1) (0,-1) (0,0) (-1,0)
+ *   s = 4: 2x2: phases (0,0) (0,3) (3,0) (3,3), the four corner pixels as above with corner (i + [a == 3], j + [b == 3])
+ *          1x2: phases (1,0) (1,3) (2,0) (2,3), pixels (ci, cj-1) (ci, cj)
+ *          2x1: phases (0,1) (0,2) (3,1) (3,2), pixels (ci, cj) (ci-1, cj)
+ *          1x1: phases (1,1) (1,2) (2,1) (2,2), pixel (ci, cj)
+ * bias9 [9][Cout] float: the ConvT bias pushed through the in-bounds taps of the 3x3 conv, per class
+ * (top / middle / bottom row of Y) x (left / middle / right column): bias9[3 r + c] = sum of Wr[dy][dx] bt over the
+ * taps the zero padding leaves at that class.  Added in fp32 before the one rounding to fp16.
+ * Route: a corner im2col of X into ws ([BT (h+1) (w+1), 4 Cin] half, vda_subpixel_conv_workspace bytes), then one
+ * launch of the phased 256x256 GEMM per group on a K slice of it.  Cout == 256, Cin % 64 == 0, s in {2, 4}, all
+ * buffers 16-byte aligned and below 2 GiB; vda_subpixel_conv_check returns 0 for a shape that is served, else -22
+ * (message in vda_last_error), without a launch.  fp16 only.
+ */
+int vda_subpixel_conv(const void* x, const void* w, const float* bias9, void* y, int32_t BT, int32_t h, int32_t w_,
+                      int32_t Cin, int32_t Cout, int32_t s, void* ws, int64_t ws_bytes, void* stream);
+int64_t vda_subpixel_conv_workspace(int32_t BT, int32_t h, int32_t w_, int32_t Cin, int32_t s);
+int vda_subpixel_conv_check(int32_t BT, int32_t h, int32_t w_, int32_t Cin, int32_t Cout, int32_t s);
 
 /*
  * Row LayerNorm, fp32 statistics.  X rows of C halfs (row stride ldx); Y [rows, C] half.

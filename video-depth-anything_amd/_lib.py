@@ -22,7 +22,8 @@ if os.environ.get("VDA_LIB_OVERRIDE"):  # tuning builds: the op library linked n
 EXPORTED = (
     "vda_version", "vda_epilogue_size", "vda_last_error", "vda_gemm", "vda_gemm_check", "vda_conv2d", "vda_conv2d_workspace",
     "vda_layernorm",
-    "vda_conv2d_res2_upsample_ok",
+    "vda_conv2d_res2_upsample_ok", "vda_conv2d_bias9_ok",
+    "vda_subpixel_conv", "vda_subpixel_conv_workspace", "vda_subpixel_conv_check",
     "vda_row_stats", "vda_groupnorm", "vda_groupnorm_workspace",
     "vda_groupnorm_linear", "vda_groupnorm_linear_workspace", "vda_groupnorm_linear_fused",
     "vda_spatial_attention", "vda_temporal_attention", "vda_upsample_bilinear", "vda_patch_im2col",
@@ -64,7 +65,7 @@ class Epilogue(ctypes.Structure):
         ("ps_cout", c_int32), ("ps_hin", c_int32), ("ps_win", c_int32),
         ("ln_stats", c_void_p), ("ln_colsum", c_void_p), ("ln_parts", c_int32), ("ln_eps", c_float),
         ("stats_out", c_void_p), ("res2_h", c_int32), ("res2_w", c_int32), ("sched", c_void_p),
-        ("drop_period", c_int32),
+        ("drop_period", c_int32), ("bias9", c_void_p),
     ]
 
 
@@ -84,6 +85,10 @@ def _declare(lib):
         "vda_conv2d": ([P, P, P, I, I, I, I, I, I, I, I, I, I, I, EP, P, L, P], I),
         "vda_conv2d_workspace": ([I, I, I, I, I, I, I, I], L),
         "vda_conv2d_res2_upsample_ok": ([I, I, I, I, I, I, I, I], I),
+        "vda_conv2d_bias9_ok": ([I, I, I, I, I, I, I], I),
+        "vda_subpixel_conv": ([P, P, P, P, I, I, I, I, I, I, P, L, P], I),
+        "vda_subpixel_conv_workspace": ([I, I, I, I, I], L),
+        "vda_subpixel_conv_check": ([I, I, I, I, I, I], I),
         "vda_layernorm": ([P, L, P, P, P, I, I, F, I, P], I),
         "vda_row_stats": ([P, L, P, I, I, F, P], I),
         "vda_groupnorm": ([P, P, P, P, I, I, I, I, F, P, P], I),

@@ -50,6 +50,12 @@ extern "C" int vda_conv2d_res2_upsample_ok(int32_t BT, int32_t H, int32_t W, int
   return conv_takes_hconv(BT, H, W, Cin, Cout, ks, stride, pad) ? 1 : 0;
 }
 
+extern "C" int vda_conv2d_bias9_ok(int32_t BT, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t up_h,
+                                   int32_t up_w) {
+  if (BT <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || up_h <= 0 || up_w <= 0 || g_force_tile >= 0) return 0;
+  return vda_conv_halo_fused_serves(BT, H, W, up_h, up_w, Cin, Cout) ? 1 : 0;
+}
+
 extern "C" int vda_conv2d(const void* x, const void* w, void* y, int32_t BT, int32_t H, int32_t W,
                           int32_t Cin, int32_t Cout, int32_t ks, int32_t stride, int32_t pad,
                           int32_t pre_relu, int32_t up_h, int32_t up_w, const vda_epilogue* epi,
@@ -88,13 +94,19 @@ extern "C" int vda_conv2d(const void* x, const void* w, void* y, int32_t BT, int
     return vda_conv_hconv(x, w, y, p.epi.bias, p.epi.act == VDA_ACT_RELU, pre_relu, p.epi.res, p.epi.res2,
                           p.epi.res2_h, p.epi.res2_w, BT, H, W, Cin, Cout, (hipStream_t)stream);
   }
+  // a 9-class bias table exists in the halo conv with the fused resize only
+  VDA_CHECK_ARG(!p.epi.bias9 || (!p.epi.bias && (uintptr_t)p.epi.bias9 % 16 == 0 && ks == 3 && stride == 1 && pad == 1 &&
+                                 !pre_relu && !p.epi.res && !p.epi.res2 && !p.epi.gamma && !p.epi.rowbias &&
+                                 vda_conv2d_bias9_ok(BT, H, W, Cin, Cout, p.up_h, p.up_w)),
+                "bias9: the 3x3 conv through a fused resize only (vda_conv2d_bias9_ok), 16-byte aligned, in place "
+                "of bias, no residual / gamma / rowbias / pre-ReLU");
   if (p.up_h > 0) {
     // 3x3 conv on a bilinear resize with 128 outputs (output_conv1 on refinenet1's x2 resize): the
     // halo conv with the resize fused into its patch staging (bit-identical to resize + conv)
     if (g_force_tile < 0 && ks == 3 && stride == 1 && pad == 1 && !pre_relu && !p.epi.res && !p.epi.res2 &&
         !p.epi.gamma && !p.epi.rowbias) {
       rc = vda_conv_halo_fused(x, w, y, p.epi.bias, p.epi.act == VDA_ACT_RELU, BT, H, W, p.up_h, p.up_w, Cin, Cout,
-                               (hipStream_t)stream);
+                               (hipStream_t)stream, p.epi.bias9);
       if (rc != 1) return rc;
     }
     return vda_launch_conv_reg(p, (hipStream_t)stream);

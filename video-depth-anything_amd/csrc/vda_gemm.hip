@@ -204,6 +204,7 @@ int gemm_check(const void* x, int64_t ldx, const void* w, void* y, int64_t ldy, 
   if (p.epi.rmod <= 0) p.epi.rmod = 1;
   const vda_epilogue& e = p.epi;
   VDA_CHECK_ARG(e.res2_h == 0 && e.res2_w == 0, "upsampled res2: vda_conv2d only");
+  VDA_CHECK_ARG(!e.bias9, "bias9: vda_conv2d only");
   // Two epilogue options exist in one kernel each, so the call must be one the automatic route gives to
   // that kernel (any other kernel would store all M rows, or ignore the row bias); what is left here are
   // those kernels' own preconditions.
@@ -297,6 +298,17 @@ extern "C" int vda_gemm(const void* x, int64_t ldx, const void* w, void* y, int6
 }
 
 int vda_launch_conv_gemm(const GemmParams& p, hipStream_t st) { return launch<true>(p, st); }
+
+int vda_launch_subpixel_gemm(const GemmParams& p, hipStream_t st) {
+  if (!phased_dense_ok(p.M, p.N, p.K, p.ldx) || p.N % 256 != 0 || p.N > 8 * 256)
+    return vda_set_error(-22, "sub-pixel conv: K % 64 == 0, N = 256 phases (<= 8), operands below 2 GiB");
+  const int tiles_m = (p.M + 255) / 256, tiles_n = p.N / 256;
+  const int grid = phased_sched(tiles_m * tiles_n, false);
+  hipLaunchKernelGGL((gemm256_kernel<2, 2, false, VDA_ACT_NONE, false, false, 0, true>), dim3(grid), dim3(512), 0, st, p,
+                     tiles_m, tiles_n);
+  VDA_LAUNCH_CHECK();
+  return 0;
+}
 
 int vda_launch_depth_gemm(const GemmParams& p, hipStream_t st) {
   const int tiles_m = (p.M + 255) / 256;

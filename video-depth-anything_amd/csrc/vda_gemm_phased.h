@@ -209,7 +209,13 @@ constexpr int phased_nit() {
 // fold and a per-frame row bias (the motion modules' q/k/v).  The fixed kinds carry no runtime branches
 // on the epilogue, which keeps the uniform state of the persistent loop in SGPRs (no spill reloads,
 // whose vmcnt(0) would drain the chained stores at every tile start).
-template <int XR, int WR, bool CONV, int ACT, bool ROWB, bool LNF, int EK>  // X / W operand regions of 128 rows (BM = 128 XR, BN = 128 WR)
+// SUBP: the sub-pixel conv route (vda_subpixel_conv): tile row m is a corner (bt, ci, cj) of the (H + 1) x
+// (W + 1) corner grid of a [BT, H, W] source map, N tile t holds the 256 channels of phase (a, b) =
+// p.sp_phases nibble t, and the row is output pixel (s i + a, s j + b) of source pixel i = ci - (a == s - 1),
+// j = cj - (b == s - 1) (s = p.stride; rows whose source pixel lies outside the map are not stored).  The bias
+// comes from the 9-class table p.sp_bias [9][256] (top / middle / bottom output row x left / middle / right
+// column) in fp32 on the accumulators; the store writes whole 512-B pixel runs like the pixel shuffle.
+template <int XR, int WR, bool CONV, int ACT, bool ROWB, bool LNF, int EK, bool SUBP = false>  // X / W operand regions of 128 rows (BM = 128 XR, BN = 128 WR)
 __device__ __forceinline__ int gemm256_tile(const GemmParams& p, int vb, int tiles_m, int tiles_n, h16* smem,
                                             bool pre, int vb_next, int wave_in, unsigned* tctr = nullptr,
                                             int tbase = 0, int* tslot = nullptr) {
@@ -226,6 +232,8 @@ __device__ __forceinline__ int gemm256_tile(const GemmParams& p, int vb, int til
   static_assert(!(LNF && (ROWB || CONV)), "LNF: dense, no row bias");
   static_assert(EK == 0 || (!CONV && !ROWB), "fixed epilogue kinds: dense, no row bias");
   static_assert(EK != 3 || (ACT == VDA_ACT_NONE && LNF), "EK 3: LN fold + per-frame row bias, no activation");
+  static_assert(!SUBP || (XR == 2 && WR == 2 && !CONV && ACT == VDA_ACT_NONE && !ROWB && !LNF && EK == 0),
+                "SUBP: dense 256x256, staged epilogue, no activation");
   const bool has_bias = EK ? true : p.epi.bias != nullptr;
   const bool has_gamma = EK ? false : p.epi.gamma != nullptr;
   // ConvTranspose(k = s) pixel-shuffle stores through the staged row epilogue when a 256-wide N tile is
@@ -236,7 +244,7 @@ __device__ __forceinline__ int gemm256_tile(const GemmParams& p, int vb, int til
   const bool ps_rows = !EK && ACT != VDA_ACT_GEGLU && !ROWB && XR == 2 && WR == 2 &&
                        p.epi.store == VDA_STORE_PIXEL_SHUFFLE && p.epi.ps_cout % 256 == 0 && p.epi.ps_win >= 16 &&
                        (long)p.M * p.N * 2 < 0x7fffffffL && (uintptr_t)p.y % 16 == 0;
-  const bool rows_store = EK ? true : (p.epi.store == VDA_STORE_ROWS || ps_rows);
+  const bool rows_store = (EK || SUBP) ? true : (p.epi.store == VDA_STORE_ROWS || ps_rows);
   const bool has_res = EK ? false : p.epi.res != nullptr;
   const bool has_res2 = EK ? false : p.epi.res2 != nullptr;
   const bool has_stats = EK ? false : p.epi.stats_out != nullptr;
@@ -819,6 +827,38 @@ __device__ __forceinline__ int gemm256_tile(const GemmParams& p, int vb, int til
         }
       }
     }
+    if constexpr (SUBP) {  // + bias9[class of the row's output pixel]: the row walk advances (cj, ci) by 16 rows
+      const int s = p.stride, hc = p.H + 1, wc = p.W + 1;
+      const int ph = (p.sp_phases >> (4 * tile_n)) & 15, pa = ph >> 2, pb = ph & 3;
+      const int m = m0 + wm * 128 + mcol;
+      int cj = m % wc, ci = (m / wc) % hc;
+      // the middle class (every pixel off the map's outer ring) stays in registers; a row on the ring loads
+      // its own class's vector instead (one row group at a time: the accumulators leave no room for more)
+      const float* bcol = p.sp_bias + wn * 64 + nq;
+      f4 bmid[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) bmid[i] = *reinterpret_cast<const f4*>(bcol + 4 * 256 + i * 16);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int si = ci - (pa == s - 1 ? 1 : 0), sj = cj - (pb == s - 1 ? 1 : 0);
+        const int yc = (pa == 0 && si == 0) ? 0 : (pa == s - 1 && si == p.H - 1) ? 2 : 1;
+        const int xc = (pb == 0 && sj == 0) ? 0 : (pb == s - 1 && sj == p.W - 1) ? 2 : 1;
+        const int cls = yc * 3 + xc;
+        if (cls == 4) {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) acc[i][j] += bmid[i];
+        } else {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) acc[i][j] += *reinterpret_cast<const f4*>(bcol + cls * 256 + i * 16);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        cj += 16;
+        while (cj >= wc) {
+          cj -= wc;
+          if (++ci == hc) ci = 0;
+        }
+      }
+    }
     // gamma (layer scale) is normally folded into W and b by the host; the multiply is compiled
     // only into the has-gamma variant of the loop, and fp32 -> fp16 goes through v_cvt_pk_f16_f32
     if constexpr (TAB) {
@@ -1029,7 +1069,38 @@ __device__ __forceinline__ int gemm256_tile(const GemmParams& p, int vb, int til
       }
       }
     };
-    if (ps_rows) {
+    // sub-pixel conv (SUBP): tile row m = corner (bt, ci, cj), its 256 columns = the channels of output pixel
+    // (s i + a, s j + b); corners whose source pixel (i, j) is outside the map store nothing
+    auto sp_store = [&]() {
+      if constexpr (SUBP) {
+        const int s = p.stride, hin = p.H, win = p.W, hc = hin + 1, wc = win + 1;
+        const int ph = (p.sp_phases >> (4 * tile_n)) & 15, pa = ph >> 2, pb = ph & 3;
+        const int ea = pa == s - 1 ? 1 : 0, eb = pb == s - 1 ? 1 : 0;
+        const __amdgpu_buffer_rsrc_t rz = __builtin_amdgcn_make_buffer_rsrc(
+            (void*)p.y, (short)0, (int)((long)p.sp_bt * hin * s * win * s * 256 * 2), 0x00020000);
+        int m = m0 + row0;
+        int cj = m % wc, tq = m / wc;
+        int ci = tq % hc, bt = tq / hc;
+        const long rowlen = (long)win * s;
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+          const int si = ci - ea, sj = cj - eb;
+          const bool ok = m < p.M && (unsigned)si < (unsigned)hin && (unsigned)sj < (unsigned)win;
+          const long pix = ((long)(bt * hin + si) * s + pa) * rowlen + (long)sj * s + pb;
+          const unsigned off = ok ? (unsigned)((pix * 256 + q * 8) * 2) : 0x80000000u;
+          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, tv[it]), rz, off, 0, VDA_EPI_STORE_AUX);
+          m += RPI;
+          cj += RPI;
+          while (cj >= wc) {
+            cj -= wc;
+            if (++ci == hc) { ci = 0; ++bt; }
+          }
+        }
+      }
+    };
+    if constexpr (SUBP) {
+      sp_store();
+    } else if (ps_rows) {
       ps_store();
     } else if (nres == 0) {
       if constexpr (RPF) {
@@ -1094,7 +1165,7 @@ __device__ __forceinline__ int gemm256_tile(const GemmParams& p, int vb, int til
 // Persistent: one block per CU walks tiles vb, vb + gridDim.x, ... (virtual block ids keep the
 // XCD-aware tile mapping of a one-tile-per-block grid).  All blocks run equal-length tiles and start
 // together (starting some of them late was measured and dropped: see phased_sched in vda_gemm.hip).
-template <int XR, int WR, bool CONV, int ACT, bool ROWB, bool LNF = false, int EK = 0>
+template <int XR, int WR, bool CONV, int ACT, bool ROWB, bool LNF = false, int EK = 0, bool SUBP = false>
 __global__ __launch_bounds__(512) void gemm256_kernel(GemmParams p, int tiles_m, int tiles_n) {
   constexpr int BUF = (XR + WR) * 128 * BK;
   constexpr bool TAB = XR == 2 && (ACT == VDA_ACT_GELU || ACT == VDA_ACT_GEGLU);
@@ -1125,8 +1196,8 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmParams p, int tiles_m,
     for (int vb = blockIdx.x; vb >= 0 && vb < ntiles;) {
       TS(0);
       const int nxt = vb + (int)gridDim.x;
-      vb = gemm256_tile<XR, WR, CONV, ACT, ROWB, LNF, EK>(p, vb, tiles_m, tiles_n, smem, pre, nxt < ntiles ? nxt : -1,
-                                                         wave, tctr, tbase, tslot);
+      vb = gemm256_tile<XR, WR, CONV, ACT, ROWB, LNF, EK, SUBP>(p, vb, tiles_m, tiles_n, smem, pre,
+                                                               nxt < ntiles ? nxt : -1, wave, tctr, tbase, tslot);
       if (!chain) __syncthreads();
       pre = chain;
       TS(7);

@@ -15,6 +15,10 @@ struct GemmParams {
   // implicit conv geometry (conv mode only)
   int H, W, Cin, Ho, Wo, ks, stride, pad, pre_relu, up_h, up_w;
   vda_epilogue epi;
+  // sub-pixel conv route only (vda_launch_subpixel_gemm; with H, W = the source map and stride = s): frames,
+  // the (a << 2 | b) phase of each 256-wide N tile as nibbles, the [9][256] class bias table
+  int sp_bt, sp_phases;
+  const float* sp_bias;
 };
 // vda_debug_force_tile (tuning build): tile configuration / route override read by the GEMM launcher and
 // by the conv and depth-head routers; -1 = automatic
@@ -28,6 +32,10 @@ int vda_launch_conv_gemm(const GemmParams& p, hipStream_t st);
 // the sizes the phased 256x256 dense kernel serves: X [M, K] of row stride ldx, W [N, K] (the route's own
 // term, for a caller that builds X for that kernel)
 bool vda_gemm_phased256_serves(long M, long N, long K, long ldx);
+// one phase group of the sub-pixel conv (vda_subpixel.hip): the dense phased 256x256 kernel on the corner
+// matrix X [M = sp_bt (H + 1) (W + 1), K] (row stride ldx), W [256 nph, K], with the class bias and the
+// corner -> output pixel store of gemm256_tile's SUBP epilogue; any M >= 1, K % 64 == 0
+int vda_launch_subpixel_gemm(const GemmParams& p, hipStream_t st);
 // implicit-GEMM conv whose loader resizes its input bilinearly (p.up_h / p.up_w), register-staged
 int vda_launch_conv_reg(const GemmParams& p, hipStream_t st);
 // implicit-GEMM depth tail (3x3 C -> 32 hi/lo rows, ReLU, 1x1, ReLU; fp32 depth), 256x64 tiles
@@ -36,8 +44,10 @@ int vda_launch_depth_gemm(const GemmParams& p, hipStream_t st);
 // ---- vda_oc1.hip: halo-tiled 3x3 conv, Cout = 128 (output_conv1), plain and with the resize fused ----
 int vda_conv_halo(const void* x, const void* w, void* y, const float* bias, int relu, int BT, int H, int W, int Cin,
                   int Cout, hipStream_t st);
+// bias9: the [9][Cout] class table of vda_epilogue.bias9 in place of bias, or NULL
 int vda_conv_halo_fused(const void* x, const void* w, void* y, const float* bias, int relu, int BT, int Hs, int Ws,
-                        int H, int W, int Cin, int Cout, hipStream_t st);
+                        int H, int W, int Cin, int Cout, hipStream_t st, const float* bias9 = nullptr);
+bool vda_conv_halo_fused_serves(int BT, int Hs, int Ws, int H, int W, int Cin, int Cout);
 
 // ---- vda_dconv.hip: depth-tail conv on the resized map, 2 blocks / CU ----
 bool vda_depth_conv_serves(int H, int W, int C);

@@ -53,7 +53,8 @@ template <bool UPS>
 __global__ __launch_bounds__(UPS ? 768 : 512) void halo_conv_kernel(const h16* __restrict__ U, const h16* __restrict__ w1,
                                                                   const float* __restrict__ b1, h16* __restrict__ yout,
                                                                   int relu_out, int H, int W, int C, int tiles_x,
-                                                                  int tiles_y, int ntiles, int Hs = 0, int Ws = 0) {
+                                                                  int tiles_y, int ntiles, int Hs = 0, int Ws = 0,
+                                                                  const float* __restrict__ b9 = nullptr) {
   constexpr int IW = UPS ? 4 : 0;                        // interpolation waves
   constexpr int PSLOT = DNPIX * PSTR;                    // 16-B slots of one patch slab
   constexpr int PP = (PSLOT + 63) / 64;                  // 1-KiB DMA pieces per slab
@@ -254,11 +255,14 @@ __global__ __launch_bounds__(UPS ? 768 : 512) void halo_conv_kernel(const h16* _
 #pragma unroll
     for (int i = 0; i < 4; ++i) acc[a][i] = f4{0.f, 0.f, 0.f, 0.f};
   // the bias, held for the whole launch (a lane's channels do not change with the tile): a load in the
-  // epilogue made every tile end wait (vmcnt(0)) for it
+  // epilogue made every tile end wait (vmcnt(0)) for it.  With a 9-class table b9 [9][CO] (vda_epilogue.bias9)
+  // the registers hold the middle class, which serves every tile off the map's outer ring; a tile that touches
+  // the ring loads each pixel's class row in its epilogue.
+  const float* bsrc = b9 ? b9 + 4 * CO : b1;
   f4 bias_r[NB];
 #pragma unroll
   for (int a = 0; a < NB; ++a)
-    bias_r[a] = b1 ? *reinterpret_cast<const f4*>(b1 + (ng * NB + a) * 16 + g * 4) : f4{0.f, 0.f, 0.f, 0.f};
+    bias_r[a] = bsrc ? *reinterpret_cast<const f4*>(bsrc + (ng * NB + a) * 16 + g * 4) : f4{0.f, 0.f, 0.f, 0.f};
   const int my_pp = (PP - 1 - wave) / 8 + 1;             // next-slab patch pieces of this wave
   constexpr int PPMAX = (PP + 7) / 8;
 
@@ -327,12 +331,19 @@ __global__ __launch_bounds__(UPS ? 768 : 512) void halo_conv_kernel(const h16* _
       const __amdgpu_buffer_rsrc_t ys = __builtin_amdgcn_make_buffer_rsrc(
           (void*)(yout + (long)bt * H * W * CO), (short)0, (int)((long)H * W * CO * 2), 0x00020000);
       const bool godd = (g & 1) != 0;
+      const bool ring = b9 != nullptr && (y0 == 0 || y0 + DT >= H || x0 == 0 || x0 + DT >= W);  // block-uniform
 #pragma unroll
       for (int a = 0; a < NB; a += 2) {
-        const f4 bv0 = bias_r[a], bv1 = bias_r[a + 1];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int y = y0 + mg * 4 + i, x = x0 + frow;
+          f4 bv0 = bias_r[a], bv1 = bias_r[a + 1];
+          if (ring) {  // pixels past the map (dropped by the store) take some class's row: the table has 9
+            const int cls = (y == 0 ? 0 : y >= H - 1 ? 2 : 1) * 3 + (x == 0 ? 0 : x >= W - 1 ? 2 : 1);
+            const float* bp = b9 + cls * CO + (ng * NB + a) * 16 + g * 4;
+            bv0 = *reinterpret_cast<const f4*>(bp);
+            bv1 = *reinterpret_cast<const f4*>(bp + 16);
+          }
           const f4 v0 = acc[a][i] + bv0, v1 = acc[a + 1][i] + bv1;
           h4 o0, o1;
 #pragma unroll
@@ -408,7 +419,7 @@ extern "C" int vda_debug_oc1_timestamps(void* host) {
 // above with the resize fused into its patch staging (UPS).  x [BT, Hs, Ws, Cin] is the map BEFORE the
 // bilinear (align_corners=True) resize to (H, W).  Returns 1 when the shape is not served.
 int vda_conv_halo_fused(const void* x, const void* w, void* y, const float* bias, int relu, int BT, int Hs, int Ws,
-                        int H, int W, int Cin, int Cout, hipStream_t st) {
+                        int H, int W, int Cin, int Cout, hipStream_t st, const float* bias9) {
   if (Cout != CO || Cin % CS != 0 || Hs > H || Ws > W || Hs < 1 || Ws < 1) return 1;
   if ((long)H * W * Cout * 2 >= (1L << 31)) return 1;  // the epilogue's per-frame buffer stores take 32-bit offsets
   if (!halo_fused_fits(Hs, Ws, H, W)) return 1;
@@ -416,9 +427,17 @@ int vda_conv_halo_fused(const void* x, const void* w, void* y, const float* bias
   if (!halo_tile_grid(BT, H, W, DT, 1, 0x7fffffffL, g)) return vda_set_error(-22, "conv: too many tiles");
   // 4 interpolation waves (1 / 2: 2571 / 2080 vs 1801 us, profiles/r05_ab_oc1_interp_waves_dconv_separable.log)
   hipLaunchKernelGGL(halo_conv_kernel<true>, dim3(g.grid), dim3(768), 0, st, (const h16*)x, (const h16*)w, bias, (h16*)y,
-                     relu, H, W, Cin, g.tiles_x, g.tiles_y, g.ntiles, Hs, Ws);
+                     relu, H, W, Cin, g.tiles_x, g.tiles_y, g.ntiles, Hs, Ws, bias9);
   VDA_LAUNCH_CHECK();
   return 0;
+}
+
+// the shapes vda_conv_halo_fused serves (no launch)
+bool vda_conv_halo_fused_serves(int BT, int Hs, int Ws, int H, int W, int Cin, int Cout) {
+  if (Cout != CO || Cin % CS != 0 || Hs > H || Ws > W || Hs < 1 || Ws < 1 || BT < 1) return false;
+  if ((long)H * W * Cout * 2 >= (1L << 31) || !halo_fused_fits(Hs, Ws, H, W)) return false;
+  HaloGrid g;
+  return halo_tile_grid(BT, H, W, DT, 1, 0x7fffffffL, g);
 }
 
 // 3x3 / stride 1 / pad 1 conv, Cin % 64 == 0, Cout == 128, epilogue +bias [ReLU] (output_conv1,

@@ -198,10 +198,38 @@ Tensor conv_transpose_ks(const Tensor& x, const Tensor& w, const Tensor& bias, i
   return out;
 }
 
+// ConvTranspose(k = s) + 3x3 conv composed into one sub-pixel conv (vda.h vda_subpixel_conv): x [BT*h*w, Cin]
+// half, w the packed phase groups (flat), bias9 [9, Cout] fp32 -> [BT, s h, s w, Cout]
+Tensor subpixel_conv(const Tensor& x, const Tensor& w, const Tensor& bias9, int64_t BT, int64_t h, int64_t w_,
+                     int64_t s) {
+  TORCH_CHECK(x.scalar_type() == at::kHalf, "vda subpixel_conv: fp16 only");
+  TORCH_CHECK(x.dim() == 2 && x.is_contiguous() && x.size(0) == BT * h * w_,
+              "vda subpixel_conv: x must be a contiguous [BT*h*w, Cin] matrix");
+  need_contig(w, at::kHalf, "w", x);
+  need_contig(bias9, at::kFloat, "bias9", x);
+  TORCH_CHECK(bias9.dim() == 2 && bias9.size(0) == 9, "vda subpixel_conv: bias9 must be [9, Cout]");
+  const int64_t Cin = x.size(1), Cout = bias9.size(1);
+  // s = 2: one 2x2 group; s = 4: 2x2 + 1x2 + 2x1 + 1x1 groups of four phases each
+  TORCH_CHECK((s == 2 || s == 4) && w.numel() == 4 * Cout * Cin * (s == 2 ? 4 : 9),
+              "vda subpixel_conv: w must hold the packed phase groups of s = ", s);
+  Tensor out = at::empty({BT, h * s, w_ * s, Cout}, x.options());
+  if (x.is_meta()) return out;
+  const at::OptionalDeviceGuard g(x.device());
+  check_rc(vda_subpixel_conv_check((int32_t)BT, (int32_t)h, (int32_t)w_, (int32_t)Cin, (int32_t)Cout, (int32_t)s),
+           "vda_subpixel_conv_check");
+  const int64_t wsb = vda_subpixel_conv_workspace((int32_t)BT, (int32_t)h, (int32_t)w_, (int32_t)Cin, (int32_t)s);
+  Tensor ws = at::empty({wsb}, x.options().dtype(at::kByte));
+  check_rc(vda_subpixel_conv(x.data_ptr(), w.data_ptr(), (const float*)bias9.data_ptr(), out.data_ptr(), (int32_t)BT,
+                             (int32_t)h, (int32_t)w_, (int32_t)Cin, (int32_t)Cout, (int32_t)s, ws.data_ptr(), wsb,
+                             stream_of(x)),
+           "vda_subpixel_conv");
+  return out;
+}
+
 // ---- NHWC conv ---------------------------------------------------------------------------------
 Tensor upsample_bilinear(const Tensor& x, int64_t Ho, int64_t Wo);
 Tensor conv2d(const Tensor& x, const Tensor& w, int64_t ks, int64_t stride, int64_t pad, OptT bias, bool pre_relu,
-              int64_t act, OptT res, OptT res2, at::OptionalIntArrayRef up) {
+              int64_t act, OptT res, OptT res2, at::OptionalIntArrayRef up, OptT bias9) {
   const auto dt = act_dtype(x);
   TORCH_CHECK(x.dim() == 4 && x.is_contiguous(), "vda conv2d: x must be a contiguous NHWC [BT, H, W, Cin] map");
   need_contig(w, dt, "w", x);
@@ -242,6 +270,12 @@ Tensor conv2d(const Tensor& x, const Tensor& w, int64_t ks, int64_t stride, int6
   vda_epilogue e = make_epi(x, bias, c10::nullopt, 1, 1, c10::nullopt, r, r2, act, dt);
   e.res2_h = r2h;
   e.res2_w = r2w;
+  if (bias9) {  // the 9-class table in place of bias (vda.h vda_epilogue.bias9)
+    need_contig(*bias9, at::kFloat, "bias9", x);
+    TORCH_CHECK(!bias && bias9->dim() == 2 && bias9->size(0) == 9 && bias9->size(1) == Cout,
+                "vda conv2d: bias9 must be [9, Cout] and replaces bias");
+    e.bias9 = (const float*)bias9->data_ptr();
+  }
   int rc;
   if (dt == at::kFloat) {
     TORCH_CHECK(uh == 0, "vda conv2d: the fused-upsample loader is fp16-only");
@@ -776,8 +810,9 @@ TORCH_LIBRARY(vda, m) {
         "Tensor(c!)? sched=None, int drop_period=0, *, Tensor(a!) out) -> Tensor(a!)");
   m.def("row_stats(Tensor x, float eps) -> Tensor");
   m.def("conv_transpose_ks(Tensor x, Tensor w, Tensor bias, int BT, int h, int w_, int k) -> Tensor");
+  m.def("subpixel_conv(Tensor x, Tensor w, Tensor bias9, int BT, int h, int w_, int s) -> Tensor");
   m.def("conv2d(Tensor x, Tensor w, int ks=3, int stride=1, int pad=1, Tensor? bias=None, bool pre_relu=False, "
-        "int act=0, Tensor? res=None, Tensor? res2=None, int[]? up=None) -> Tensor");
+        "int act=0, Tensor? res=None, Tensor? res2=None, int[]? up=None, Tensor? bias9=None) -> Tensor");
   m.def("layernorm(Tensor x, Tensor gamma, Tensor beta, float eps, int skip_period=0, int? rows=None) -> Tensor");
   m.def("groupnorm(Tensor x, Tensor gamma, Tensor beta, int frames, int groups, float eps) -> Tensor");
   m.def("groupnorm_linear(Tensor x, Tensor gamma, Tensor beta, int frames, int groups, float eps, Tensor w, "
@@ -802,6 +837,7 @@ TORCH_LIBRARY(vda, m) {
     m.impl("gemm", &gemm);                                    \
     m.impl("gemm.out", &gemm_out);                            \
     m.impl("conv_transpose_ks", &conv_transpose_ks);          \
+    m.impl("subpixel_conv", &subpixel_conv);                  \
     m.impl("conv2d", &conv2d);                                \
     m.impl("layernorm", &layernorm);                          \
     m.impl("row_stats", &row_stats);                          \

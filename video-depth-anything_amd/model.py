@@ -243,7 +243,11 @@ class VideoDepthAnything(nn.Module):
     ``fold_tap_norm`` folds the final LayerNorm of each encoder tap into its DPT projects GEMM (the cls rows
     dropped in that GEMM's store), ``dynamic_tiles`` lets the encoder's persistent GEMMs
     take their tiles by atomic ticket (per-stream counters, ``ops.sched_counters``) instead of a fixed
-    stride.  No environment variable changes the schedule."""
+    stride, ``fold_head_linear`` composes resize_layers[0] / [1] (ConvTranspose k = s) with layer1_rn / layer2_rn
+    (3x3, no bias) into one sub-pixel conv each on the 37^2-sized projected maps (``forward`` only, fp16, heads
+    whose widths ``ops.subpixel_conv_accepts`` serves; layer_1 / layer_2 are then never written) and refinenet1's
+    1x1 out_conv into output_conv1 (one 3x3 conv with a 9-class bias table, where ``ops.conv2d_bias9_accepts``).
+    No environment variable changes the schedule."""
 
     fold_layernorms: bool = True
     epilogue_stats: bool = True
@@ -251,6 +255,7 @@ class VideoDepthAnything(nn.Module):
     fold_ff_norm: bool = False  # built and tested; same-box forward A/B 693.7 -> 690.0 frames/s (r06_ab_ffold.log)
     fuse_groupnorm_linear: bool = True
     fold_tap_norm: bool = True
+    fold_head_linear: bool = True
 
     def __init__(self, encoder="vitl", features=256, out_channels=(256, 512, 1024, 1024), use_bn=False,
                  use_clstoken=False, num_frames=32, pe="ape"):
@@ -481,6 +486,10 @@ class VideoDepthAnything(nn.Module):
         while the first forward is still writing them)."""
         P = self._pack(torch.device(device), fp32)
         self._token_bias(P, int(size[0]), int(size[1]), torch.device(device))
+        if self._head_fold(P, 1, int(size[0]) // PATCH, int(size[1]) // PATCH):
+            self._pack_subpixel(P)
+        if self._oc1_fold(P, 1, int(size[0]) // PATCH, int(size[1]) // PATCH):
+            self._pack_oc1(P)
 
     # -- forward ---------------------------------------------------------------------------
     def _qkv_fold(self, q: _Packed, M: int, S: int, T: int) -> List[bool]:
@@ -534,9 +543,10 @@ class VideoDepthAnything(nn.Module):
         h = ops.gemm(g, q.ff2_w, bias=q.ff2_b, res=h, out=h)
         return ops.gemm(h, q.pout_w, bias=q.pout_b, res=x)
 
-    def _fusion(self, q: _Packed, x0, x1, size):
+    def _fusion(self, q: _Packed, x0, x1, size, out_conv: bool = True):
         """FeatureFusionBlock (blocks.py:135-162) on NHWC maps; the 1x1 out_conv commutes with the
-        bilinear resize (both linear, resize weights sum to 1), so it runs at the low resolution."""
+        bilinear resize (both linear, resize weights sum to 1), so it runs at the low resolution.
+        ``out_conv=False`` returns the map before out_conv (the caller has composed it into the next conv)."""
         if x1 is not None:
             t = ops.conv2d(x1, q.r1c1_w, bias=q.r1c1_b, pre_relu=True, act=ACT_RELU)
             out = ops.conv2d(t, q.r1c2_w, bias=q.r1c2_b, res=x1, res2=x0)
@@ -544,6 +554,8 @@ class VideoDepthAnything(nn.Module):
             out = x0
         t = ops.conv2d(out, q.r2c1_w, bias=q.r2c1_b, pre_relu=True, act=ACT_RELU)
         out = ops.conv2d(t, q.r2c2_w, bias=q.r2c2_b, res=out)
+        if not out_conv:
+            return out, size
         BT, h, w, Cf = out.shape
         y = ops.gemm(out.view(-1, Cf), q.out_w, bias=q.out_b).view(BT, h, w, Cf)
         return y, size
@@ -631,11 +643,54 @@ class VideoDepthAnything(nn.Module):
         return all(ops.gemm_accepts(BT * ntok, w.shape[0], P.C, ln_fold=True, ln_parts=nparts, drop_period=ntok)
                    for w, _, _ in P.projf)
 
-    def _reassemble(self, P: _Packed, enc, BT: int, ph: int, pw: int) -> List[torch.Tensor]:
+    def _head_fold(self, P: _Packed, BT: int, ph: int, pw: int) -> bool:
+        """Whether ``forward`` composes resize_layers[0] / [1] with layer1_rn / layer2_rn: fp16, the switch, and
+        both shapes served by the library's sub-pixel conv route (ViT-L's 256 / 512 -> 256 channels)."""
+        if P.fp32 or not bool(self.fold_head_linear):
+            return False
+        oc, Fh = self.out_channels, self.features
+        return (ops.subpixel_conv_accepts(BT, ph, pw, oc[0], Fh, 4) and
+                ops.subpixel_conv_accepts(BT, ph, pw, oc[1], Fh, 2))
+
+    def _oc1_fold(self, P: _Packed, BT: int, ph: int, pw: int) -> bool:
+        """Whether ``forward`` composes refinenet1's out_conv (1x1, at 4ph x 4pw) into output_conv1 (3x3 on the x2
+        resize): fp16, the switch, and a shape whose conv route takes the 9-class bias table."""
+        if P.fp32 or not bool(self.fold_head_linear):
+            return False
+        Fh = self.features
+        return ops.conv2d_bias9_accepts(BT, 4 * ph, 4 * pw, Fh, Fh // 2, (8 * ph, 8 * pw))
+
+    def _pack_oc1(self, P: _Packed):
+        """output_conv1 . refinenet1.out_conv as one 3x3 conv (weights.compose_pointwise_conv3), built on first use."""
+        if getattr(P, "oc1c", None) is None:
+            from .weights import compose_pointwise_conv3
+            s, dev = self.head.scratch, P.patch_w.device
+            w, b9 = compose_pointwise_conv3(s.refinenet1.out_conv.weight, s.refinenet1.out_conv.bias,
+                                            s.output_conv1.weight, s.output_conv1.bias)
+            P.oc1c = (w.to(dev), b9.to(dev))
+        return P.oc1c
+
+    def _pack_subpixel(self, P: _Packed):
+        """Composed weights and class-bias tables of the two sub-pixel convs (weights.compose_subpixel: float64
+        products of the unrounded weights, rounded once), built on first use and kept with the packed weights."""
+        if getattr(P, "sp", None) is None:
+            from .weights import compose_subpixel
+            hd, dev = self.head, P.patch_w.device
+            P.sp = []
+            for i, s in ((0, 4), (1, 2)):
+                ct = hd.resize_layers[i]
+                w, b9 = compose_subpixel(ct.weight, ct.bias, getattr(hd.scratch, f"layer{i + 1}_rn").weight, s)
+                P.sp.append((w.to(dev), b9.to(dev)))
+        return P.sp
+
+    def _reassemble(self, P: _Packed, enc, BT: int, ph: int, pw: int, fold: bool = False) -> List[torch.Tensor]:
         """DPT reassemble (dpt_temporal.py:55-69 == get_motion_features :101-131, dpt.py:60-90):
-        enc = _encode's (taps, cls) -> layer_1..4 NHWC [BT, h, w, C]."""
+        enc = _encode's (taps, cls) -> layer_1..4 NHWC [BT, h, w, C].  With ``fold`` (``forward`` where
+        ``_head_fold`` says so) the first two are layer1_rn(layer_1) and layer2_rn(layer_2) instead, each one
+        sub-pixel conv of the projected map, for ``_head(..., folded=True)``."""
         feats, cls, projected = enc
         oc = self.out_channels
+        sp = self._pack_subpixel(P) if fold else None
         lay = []
         for i, ft in enumerate(feats):
             if cls is not None:
@@ -644,7 +699,9 @@ class VideoDepthAnything(nn.Module):
                 rb = ops.gemm(cls[i].float(), P.ro_wb[i], bias=P.ro_b[i])
                 ft = ops.gemm(ft, P.ro_wa[i], rowbias=rb, rdiv=ph * pw, rmod=BT, act=ACT_GELU)
             p = ft if projected else ops.gemm(ft, P.proj_w[i], bias=P.proj_b[i])
-            if i == 0:
+            if fold and i < 2:
+                l = ops.subpixel_conv(p, sp[i][0], sp[i][1], BT, ph, pw, 4 if i == 0 else 2)
+            elif i == 0:
                 l = ops.conv_transpose_ks(p, P.rs_w[0], P.rs_b[0], BT, ph, pw, 4)
             elif i == 1:
                 l = ops.conv_transpose_ks(p, P.rs_w[1], P.rs_b[1], BT, ph, pw, 2)
@@ -656,10 +713,12 @@ class VideoDepthAnything(nn.Module):
         return lay
 
     def _head(self, P: _Packed, l1, l2, l3, l4, B: int, T: int, ph: int, pw: int, skip_tmp_block: bool,
-              sel: Optional[List[int]] = None) -> torch.Tensor:
+              sel: Optional[List[int]] = None, folded: bool = False, fold_out: bool = False) -> torch.Tensor:
         """Temporal DPT head from the reassembled maps (dpt_temporal.py:71-99).  layer_3/4 carry all
         B*T frames.  With ``sel`` (streaming, dpt_temporal.py:181-260) layer_1/2 carry only the
-        selected frames and path_3 is cut to them after motion module 3.  -> depth [n, 14ph, 14pw] fp32."""
+        selected frames and path_3 is cut to them after motion module 3.  ``folded``: l1 / l2 already are
+        layer1_rn / layer2_rn's outputs (``_reassemble(..., fold=True)``); ``fold_out``: refinenet1's out_conv is
+        composed into output_conv1 (``_oc1_fold``).  -> depth [n, 14ph, 14pw] fp32."""
         oc = self.out_channels
         BT = B * T
         h3, w3 = l3.shape[1:3]
@@ -667,8 +726,8 @@ class VideoDepthAnything(nn.Module):
         # temporal modules on layer_3 / layer_4 (dpt_temporal.py:75-76)
         l3 = self._temporal(P.mm[0], l3.reshape(-1, oc[2]), B, T, h3 * w3).view(BT, h3, w3, oc[2])
         l4 = self._temporal(P.mm[1], l4.reshape(-1, oc[3]), B, T, h4 * w4).view(BT, h4, w4, oc[3])
-        r1 = ops.conv2d(l1, P.rn[0])
-        r2 = ops.conv2d(l2, P.rn[1])
+        r1 = l1 if folded else ops.conv2d(l1, P.rn[0])
+        r2 = l2 if folded else ops.conv2d(l2, P.rn[1])
         r3 = ops.conv2d(l3, P.rn[2])
         r4 = ops.conv2d(l4, P.rn[3])
         del l1, l2, l3, l4
@@ -686,12 +745,15 @@ class VideoDepthAnything(nn.Module):
         # refinenet2's upsample to r1's grid (blocks.py:156-158) is only refinenet1's skip input (res2 of
         # its RCU conv2, blocks.py:146-150): the conv reads it through the upsample in its epilogue
         # (bit-identical; materialised by the op where the conv route has no such epilogue)
-        y, _ = self._fusion(P.ref[1], y, r1, None)  # refinenet1: scale_factor 2
+        y, _ = self._fusion(P.ref[1], y, r1, None, out_conv=not fold_out)  # refinenet1: scale_factor 2
         H1, W1 = 2 * y.shape[1], 2 * y.shape[2]
         # refinenet1's x2 bilinear upsample (blocks.py:151-158) fused into output_conv1's patch staging
         # (fp16: the halo conv builds each patch by interpolation; fp32 mode materialises the resize)
         if P.fp32:
             o1 = ops.conv2d(ops.upsample_bilinear(y, H1, W1), P.oc1_w, bias=P.oc1_b)
+        elif fold_out:  # W_oc1[t] W_out on the map before out_conv, the bias by class of the output pixel
+            wc, b9 = self._pack_oc1(P)
+            o1 = ops.conv2d(y, wc, bias9=b9, up=(H1, W1))
         else:
             o1 = ops.conv2d(y, P.oc1_w, bias=P.oc1_b, up=(H1, W1))
         # output_conv2 with fp32 weights on the bilinear resize to (14ph, 14pw) (dpt_temporal.py:92-97);
@@ -710,9 +772,10 @@ class VideoDepthAnything(nn.Module):
         BT = B * T
         ph, pw = H // PATCH, W // PATCH
         feats = self._encode(P, x.reshape(BT, 3, H, W))
-        lay = self._reassemble(P, feats, BT, ph, pw)
+        fold = self._head_fold(P, BT, ph, pw)
+        lay = self._reassemble(P, feats, BT, ph, pw, fold=fold)
         del feats
-        depth = self._head(P, *lay, B, T, ph, pw, skip_tmp_block)
+        depth = self._head(P, *lay, B, T, ph, pw, skip_tmp_block, folded=fold, fold_out=self._oc1_fold(P, BT, ph, pw))
         return depth.view(B, T, H, W)
 
     # -- streaming mode (video_depth.py:66-327) ----------------------------------------------

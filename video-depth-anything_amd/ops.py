@@ -128,14 +128,38 @@ def conv_transpose_ks(x: Tensor, w: Tensor, bias: Tensor, BT: int, h: int, w_: i
     return _vda().conv_transpose_ks(x, w, bias, int(BT), int(h), int(w_), int(k))
 
 
+def subpixel_conv(x: Tensor, w: Tensor, bias9: Tensor, BT: int, h: int, w_: int, s: int) -> Tensor:
+    """ConvTranspose2d(kernel = stride = s) then a zero-padded 3x3 conv as ONE sub-pixel conv of the low-resolution
+    map (vda.h vda_subpixel_conv): x [BT*h*w, Cin] fp16; w the composed phase-group weights and bias9 [9, Cout]
+    fp32 of ``weights.compose_subpixel`` -> [BT, s*h, s*w, Cout].  The map between the two convs is never written."""
+    _need(x, torch.float16, "x")
+    return _vda().subpixel_conv(x, w, bias9, int(BT), int(h), int(w_), int(s))
+
+
+@functools.lru_cache(maxsize=None)
+def subpixel_conv_accepts(BT: int, h: int, w_: int, Cin: int, Cout: int, s: int) -> bool:
+    """Whether ``subpixel_conv`` serves this shape (vda.h vda_subpixel_conv_check: Cout 256, Cin % 64 == 0, s in
+    {2, 4}, buffers below 2 GiB), no launch.  Memoised per shape."""
+    return _lib.lib().vda_subpixel_conv_check(int(BT), int(h), int(w_), int(Cin), int(Cout), int(s)) == 0
+
+
+@functools.lru_cache(maxsize=None)
+def conv2d_bias9_accepts(BT: int, H: int, W: int, Cin: int, Cout: int, up) -> bool:
+    """Whether the 3x3 ``conv2d`` of [BT, H, W, Cin] through ``up=(Hu, Wu)`` takes a ``bias9`` table
+    (vda.h vda_conv2d_bias9_ok), no launch.  Memoised per shape."""
+    return _lib.lib().vda_conv2d_bias9_ok(int(BT), int(H), int(W), int(Cin), int(Cout), int(up[0]), int(up[1])) == 1
+
+
 def conv2d(x: Tensor, w: Tensor, *, ks=3, stride=1, pad=1, bias=None, pre_relu=False, act=ACT_NONE,
-           res=None, res2=None, up=None) -> Tensor:
+           res=None, res2=None, up=None, bias9=None) -> Tensor:
     """NHWC conv.  x [BT, H, W, Cin] fp16; w [Cout, ks, ks, Cin] fp16 -> [BT, Ho, Wo, Cout].
     `up=(Hu, Wu)` reads x through a bilinear align_corners=True resize to (Hu, Wu) first.
+    `bias9` [9, Cout] fp32 replaces `bias` by a per-class table over the output map's outer ring (the bias of
+    a 1x1 conv composed into this one, vda.h vda_epilogue.bias9; where ``conv2d_bias9_accepts``).
     The strip conv's split workspace comes from the caching allocator per call (no shared state)."""
     _need(x, x.dtype, "x")
     return _vda().conv2d(x, w, int(ks), int(stride), int(pad), bias, bool(pre_relu), int(act), res, res2,
-                         None if up is None else [int(up[0]), int(up[1])])
+                         None if up is None else [int(up[0]), int(up[1])], bias9)
 
 
 def layernorm(x: Tensor, gamma: Tensor, beta: Tensor, eps: float, *, skip_period: int = 0,
