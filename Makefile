@@ -24,7 +24,7 @@ build/vda_gemm.o: EXTRA := -fno-slp-vectorize
 
 build/tune/vda_attn.o: EXTRA := -fno-honor-nans -fno-slp-vectorize
 build/tune/vda_gemm.o: EXTRA := -fno-slp-vectorize
-DEPS := $(addprefix $(PKG)/csrc/,vda_common.h vda_stream.h vda_halo.h vda_internal.h vda_tune.h vda_gemm_tile.h vda_gemm_phased.h vda_preprocess.h phi_table.h) include/vda.h include/vda_tune.h
+DEPS := $(addprefix $(PKG)/csrc/,vda_common.h vda_stream.h vda_lut.h vda_halo.h vda_internal.h vda_tune.h vda_gemm_tile.h vda_gemm_phased.h vda_preprocess.h phi_table.h) include/vda.h include/vda_tune.h
 
 build/%.o: $(PKG)/csrc/%.hip $(DEPS)
 	@mkdir -p build

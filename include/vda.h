@@ -457,6 +457,90 @@ int vda_depth_colorize(const float* depth, int32_t F, int32_t H, int32_t W, cons
                        const uint8_t* lut, int32_t layout, uint8_t* out, void* stream);
 
 /*
+ * Ground-truth comparison video on the device (the reference's calculate_metrics.py:206-258 with
+ * utils/vis_util.py: visualise_data): per frame a canvas of rows x cols tiles of H x W pixels, the RGB frame,
+ * the GT depth, and per method an error map |gt - pred|, the prediction and a "stability" image (the x-t
+ * slice of the depth at one image column, filled in frame by frame), from the tensors evaluation leaves on
+ * the device straight to the bytes of the output file.  No atomics, no allocation, no synchronisation,
+ * capturable in a graph; results stay on the device.  Argument checks run before any launch.
+ *
+ * vda_depth_absdiff_range: range [2] float (DEVICE) = (min, max) over the n >= 1 elements of
+ *   e = valid ? fabsf(b - a) : 0.0f          (a = pred, b = gt: the subtraction is gt - pred, one fp32 operation)
+ *   which is the error map as displayed, zeros included (vis_util.py:84-94 over utils/metrics.py:92-98).
+ *   valid (uint8, non-zero = valid) may be NULL.  The reduction of vda_depth_range: block partials in ws, then
+ *   one block; NaNs are skipped; a and b need 4-byte alignment only.  ws: vda_depth_absdiff_range_workspace(n)
+ *   bytes of device memory owned by the caller, 4-byte aligned, no initialisation, nothing kept between calls.
+ *
+ * vda_panel_compose: for the F output frames t = t0 .. t0 + F - 1 of a scene of N frames, out holds frame
+ *   after frame a canvas of rows * H x cols * W pixels in `layout` (VDA_VIS_HWC, VDA_VIS_PLANAR444 or
+ *   VDA_VIS_PLANAR420 of vda_depth_colorize, with the canvas as the frame);
+ *   vda_panel_compose_bytes(F, rows, cols, H, W, layout) bytes, nothing is written outside them.
+ *   tiles: ntiles <= 12 descriptors in HOST memory (they travel in the kernel arguments), each in its own grid
+ *   cell (row < rows <= 4, col < cols <= 3).  A tile with frame offset o >= 0 and `frames` source frames shows
+ *   source frame s = t - o at canvas frame t; all its operands are indexed by s.  Per canvas pixel (y, px) of a
+ *   tile, with S = H * W:
+ *     VDA_TILE_RGB    a = uint8 [frames, H, W, 3] (any alignment): the pixel itself.  In VDA_VIS_HWC a copy; in
+ *                     the planar layouts BT.601 limited range in fp32, every operation rounded once, no
+ *                     contraction, the constants rounded to fp32 first:
+ *                       y = (0.299 r + 0.587 g) + 0.114 b;  u = (b - y) / 1.772;  v = (r - y) / 1.402
+ *                       Y = q(y * (219 / 255) + 16);  U = q(u * (224 / 255) + 128);  V likewise
+ *                       q(x) = clamp(rintf(x), 0, 255)          (ties to even; IEEE division)
+ *                     Outside 0 <= s < frames the pixel is black.
+ *     VDA_TILE_DEPTH  a = float [frames, H, W]: v = a[s, y, px], or 0.0f outside 0 <= s < frames (a warmed-up
+ *                     method before its first frame, vis_util.py:148-151), then lut[tile.lut][i] with the
+ *                     index rule of vda_depth_colorize over tile.range (DEVICE [2] float):
+ *                       x = (v - range[0]) / (range[1] - range[0]) * 255.0f;  i = (uint8_t)x by truncation,
+ *                       NaN or x <= 0 -> 0, x >= 255 -> 255
+ *     VDA_TILE_ERROR  a = pred, b = gt float [frames, H, W], valid uint8 [frames, H, W] or NULL:
+ *                     v = valid ? fabsf(b - a) : 0.0f, or 0.0f outside 0 <= s < frames, then as VDA_TILE_DEPTH
+ *     VDA_TILE_XT     a = float [frames, H, W], the whole video: the stability image [H, N] stretched to the
+ *                     tile's width, never materialised:  c = (px * N) / W in 64-bit integers, s = c - o,
+ *                     v = (c <= t && 0 <= s < frames) ? a[s, y, xstar] : 0.0f, then as VDA_TILE_DEPTH
+ *   A cell without a tile is black.  Black is RGB (0, 0, 0): bytes (16, 128, 128) in the planar layouts.
+ *   lut0 / lut1: the at most two distinct [256, 3] uint8 tables (DEVICE, any alignment) the tiles name, staged
+ *   once per block in LDS; as in vda_depth_colorize the kernel does not know their colour space: RGB rows for
+ *   VDA_VIS_HWC, converted YUV rows for the planar layouts.  4:2:0 chroma is (a + b + c + d + 2) >> 2 over 2x2
+ *   blocks of the canvas's converted samples, the last row / column of the canvas repeated at odd sizes: a
+ *   block straddles two tiles when H or W is odd.
+ *   Float operands 4-byte aligned, out any address (dword stores around bytewise heads and tails).
+ *   1 <= F <= 65535, 0 <= t0, t0 + F <= N, 0 <= xstar < W, rows * H * cols * W < 2^31.
+ *   vda_tile_size() is sizeof(vda_tile): a binding checks its mirror against it.
+ *   Deviations from the reference's matplotlib figure:
+ *     colour index: imshow bins a value as min(int(x * 256), 255) after Normalize; the panels use the index rule
+ *       above (* 255, truncation), so that one rule serves every depth picture the project writes.  The end
+ *       colours for out-of-range values are the same.
+ *     frame pairing: the reference's plot shows a warmed-up method one frame late against the GT it is
+ *       subtracted from (vis_util.py:148, :157-164 index t - t_warmup with t_warmup = o), while its logged
+ *       numbers pair gt[o + k] with pred[k] (calculate_metrics.py:223-226).  The panels follow the numbers.
+ *     axes and text: no axes, titles, legend or line plot; tiles abut.
+ */
+enum {
+  VDA_TILE_RGB = 0,
+  VDA_TILE_DEPTH = 1,
+  VDA_TILE_ERROR = 2,
+  VDA_TILE_XT = 3
+};
+typedef struct vda_tile {
+  int32_t kind;          /* VDA_TILE_* */
+  int32_t row, col;      /* the grid cell */
+  int32_t offset;        /* o: canvas frame t shows source frame t - o */
+  int32_t frames;        /* source frames */
+  int32_t lut;           /* 0 or 1: lut0 / lut1 (not RGB) */
+  const void* a;         /* RGB: uint8 frames; DEPTH, XT: float depth; ERROR: pred */
+  const float* b;        /* ERROR: gt */
+  const uint8_t* valid;  /* ERROR: mask or NULL */
+  const float* range;    /* DEVICE [2] (min, max) (not RGB) */
+} vda_tile;
+int64_t vda_tile_size(void);
+int64_t vda_depth_absdiff_range_workspace(int64_t n);
+int vda_depth_absdiff_range(const float* a, const float* b, const uint8_t* valid, int64_t n, float* range, void* ws,
+                            int64_t ws_bytes, void* stream);
+int64_t vda_panel_compose_bytes(int32_t F, int32_t rows, int32_t cols, int32_t H, int32_t W, int32_t layout);
+int vda_panel_compose(const vda_tile* tiles, int32_t ntiles, int32_t rows, int32_t cols, int32_t F, int32_t t0,
+                      int32_t N, int32_t H, int32_t W, int32_t xstar, const uint8_t* lut0, const uint8_t* lut1,
+                      int32_t layout, uint8_t* out, void* stream);
+
+/*
  * Planar YUV frames, as a YUV4MPEG2 (.y4m) file holds them, to RGB and to the network input, so that a video
  * is uploaded as the bytes of its file (1.5 B per pixel at 4:2:0) and never decoded on the host.  No atomics, no
  * allocation, no synchronisation, capturable in a graph.

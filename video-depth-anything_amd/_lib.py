@@ -31,6 +31,8 @@ EXPORTED = (
     "vda_scale_shift", "vda_scale_shift_workspace", "vda_depth_align",
     "vda_depth_eval_workspace", "vda_depth_eval_fit", "vda_depth_eval_metrics",
     "vda_depth_range_workspace", "vda_depth_range", "vda_depth_colorize_bytes", "vda_depth_colorize",
+    "vda_tile_size", "vda_depth_absdiff_range_workspace", "vda_depth_absdiff_range", "vda_panel_compose_bytes",
+    "vda_panel_compose",
     "vda_yuv_to_rgb", "vda_preprocess_yuv_workspace", "vda_preprocess_yuv",
     "vda_resample_taps", "vda_resample_tables", "vda_yuv_downscale_ok", "vda_yuv_downscale_workspace",
     "vda_yuv_downscale",
@@ -45,6 +47,7 @@ TUNE_LIB_PATH = os.path.join(os.path.dirname(_HERE), "build", "tune", "libvda.so
 ACT_NONE, ACT_GELU, ACT_GEGLU, ACT_RELU = 0, 1, 2, 3
 STORE_ROWS, STORE_PIXEL_SHUFFLE = 0, 1
 VIS_INDEX, VIS_HWC, VIS_PLANAR444, VIS_PLANAR420 = 0, 1, 2, 3  # VDA_VIS_* (vda_depth_colorize layouts)
+TILE_RGB, TILE_DEPTH, TILE_ERROR, TILE_XT = 0, 1, 2, 3  # VDA_TILE_* (vda_panel_compose tile kinds)
 YUV_420, YUV_422, YUV_444, YUV_MONO = 0, 1, 2, 3  # VDA_YUV_* (vda_yuv_to_rgb / vda_preprocess_yuv chroma codes)
 
 
@@ -66,6 +69,14 @@ class Epilogue(ctypes.Structure):
         ("ln_stats", c_void_p), ("ln_colsum", c_void_p), ("ln_parts", c_int32), ("ln_eps", c_float),
         ("stats_out", c_void_p), ("res2_h", c_int32), ("res2_w", c_int32), ("sched", c_void_p),
         ("drop_period", c_int32), ("bias9", c_void_p),
+    ]
+
+
+class Tile(ctypes.Structure):
+    """Mirror of ``vda_tile`` (include/vda.h)."""
+    _fields_ = [
+        ("kind", c_int32), ("row", c_int32), ("col", c_int32), ("offset", c_int32), ("frames", c_int32),
+        ("lut", c_int32), ("a", c_void_p), ("b", c_void_p), ("valid", c_void_p), ("range", c_void_p),
     ]
 
 
@@ -114,6 +125,11 @@ def _declare(lib):
         "vda_depth_range": ([P, L, P, P, L, P], I),
         "vda_depth_colorize_bytes": ([I, I, I, I], L),
         "vda_depth_colorize": ([P, I, I, I, P, P, I, P, P], I),
+        "vda_tile_size": ([], L),
+        "vda_depth_absdiff_range_workspace": ([L], L),
+        "vda_depth_absdiff_range": ([P, P, P, L, P, P, L, P], I),
+        "vda_panel_compose_bytes": ([I, I, I, I, I, I], L),
+        "vda_panel_compose": ([POINTER(Tile), I, I, I, I, I, I, I, I, I, P, P, I, P, P], I),
         "vda_yuv_to_rgb": ([P, I, I, I, L, I, P, P], I),
         "vda_preprocess_yuv_workspace": ([I, I, I, I, I], L),
         "vda_preprocess_yuv": ([P, I, I, I, L, I, P, I, I, POINTER(F), POINTER(F), P, L, P], I),
@@ -162,6 +178,9 @@ def lib():
         if l.vda_epilogue_size() != ctypes.sizeof(Epilogue):  # the ctypes mirror must match include/vda.h
             raise OSError(f"vda_epilogue is {l.vda_epilogue_size()} bytes in the library, {ctypes.sizeof(Epilogue)} "
                           f"in _lib.Epilogue: rebuild libvda.so or update the mirror")
+        if l.vda_tile_size() != ctypes.sizeof(Tile):
+            raise OSError(f"vda_tile is {l.vda_tile_size()} bytes in the library, {ctypes.sizeof(Tile)} in _lib.Tile: "
+                          f"rebuild libvda.so or update the mirror")
     except OSError as e:  # pragma: no cover - depends on the runtime
         _load_error = f"failed to load {LIB_PATH}: {e}"
         raise VDAUnavailable(_load_error) from e

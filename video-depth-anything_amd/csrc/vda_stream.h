@@ -1,6 +1,6 @@
 // The streaming pass: the skeleton shared by the HBM-bound, one-pass kernels over a flat run of n fp32
-// elements (vda_align.hip, vda_eval.hip, vda_vis.hip).  What a kernel does with an element is its own; how
-// the run is cut up, walked and reduced is defined here and nowhere else.
+// elements (vda_align.hip, vda_eval.hip, vda_vis.hip, vda_compare.hip).  What a kernel does with an element
+// is its own; how the run is cut up, walked and reduced is defined here and nowhere else.
 //
 // The split.  A run is head + 4 * nvec + tail elements: the head (0..3) ends at the first boundary the
 // body's vector access needs, the body is nvec groups of 4, the tail (0..3) is what is left.  Two rules
@@ -13,7 +13,8 @@
 // The reduction.  Deterministic, no atomics: per thread -> wave butterfly -> the block's waves added in
 // wave order (block_store_partial) -> per-block partials in the caller's workspace -> one wave adds the
 // partials in index order (wave_add_partials).  The number of blocks (stream_grid) is therefore part of
-// the summation order and of the workspace size.
+// the summation order and of the workspace size.  Minima and maxima (block_store_range) take the same two
+// stages; they are order-independent, so their result is exact.
 #pragma once
 #include "vda_common.h"
 
@@ -79,6 +80,45 @@ __device__ __forceinline__ void block_store_partial(const double (&s)[K], double
     for (int w = 1; w < kStreamWaves; ++w) a += red[w][threadIdx.x];
     part[threadIdx.x] = a;
   }
+}
+
+__device__ __forceinline__ float wave_min(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+// The block's (min, max) to out[0], out[1]: waves through LDS, thread 0 stores.
+__device__ __forceinline__ void block_store_range(float mn, float mx, float* __restrict__ out) {
+  __shared__ float red[kStreamWaves][2];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  mn = wave_min(mn);
+  mx = wave_max(mx);
+  if (lane == 0) {
+    red[wave][0] = mn;
+    red[wave][1] = mx;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int w = 1; w < kStreamWaves; ++w) {
+      mn = fminf(mn, red[w][0]);
+      mx = fmaxf(mx, red[w][1]);
+    }
+    out[0] = mn;
+    out[1] = mx;
+  }
+}
+
+// One block: the (min, max) of the nparts block partials at part [nparts, 2] to range[0], range[1].
+__device__ __forceinline__ void block_reduce_ranges(const float* __restrict__ part, int nparts,
+                                                    float* __restrict__ range) {
+  float mn = __builtin_inff(), mx = -__builtin_inff();
+  for (int b = threadIdx.x; b < nparts; b += kStreamBlock) {
+    mn = fminf(mn, part[2 * b]);
+    mx = fmaxf(mx, part[2 * b + 1]);
+  }
+  block_store_range(mn, mx, range);
 }
 
 // One wave: lane l adds partials l, l + 64, ... (partial b at part[b * stride ..]) in index order, a

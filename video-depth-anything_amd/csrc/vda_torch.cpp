@@ -706,6 +706,113 @@ Tensor depth_colorize(const Tensor& depth, const Tensor& range, OptT lut, int64_
   return out;
 }
 
+// ---- ground-truth comparison video ---------------------------------------------------------------
+Tensor depth_absdiff_range(const Tensor& a, const Tensor& b, OptT valid) {
+  TORCH_CHECK(a.scalar_type() == at::kFloat && a.is_contiguous() && a.numel() >= 1,
+              "vda depth_absdiff_range: a must be a contiguous, non-empty float tensor");
+  need_contig(b, at::kFloat, "b", a);
+  TORCH_CHECK(b.numel() == a.numel(), "vda depth_absdiff_range: b must have a's number of elements");
+  if (valid) {
+    need_contig(*valid, at::kByte, "valid", a);
+    TORCH_CHECK(valid->numel() == a.numel(), "vda depth_absdiff_range: valid must have a's number of elements");
+  }
+  Tensor range = at::empty({2}, a.options());
+  if (a.is_meta()) return range;
+  const at::OptionalDeviceGuard g(a.device());
+  const int64_t n = a.numel();
+  const int64_t wsb = vda_depth_absdiff_range_workspace(n);
+  Tensor ws = at::empty({wsb}, a.options().dtype(at::kByte));
+  check_rc(vda_depth_absdiff_range((const float*)a.data_ptr(), (const float*)b.data_ptr(), (const uint8_t*)ptr(valid), n,
+                                   (float*)range.data_ptr(), ws.data_ptr(), wsb, stream_of(a)),
+           "vda_depth_absdiff_range");
+  return range;
+}
+
+// Tile i: kind[i] in cell (row[i], col[i]) with frame offset offset[i] and table lut[i]; a[i] its source
+// ([n, H, W, 3] uint8 for VDA_TILE_RGB, [n, H, W] float otherwise), b[i] / valid[i] the second operand and the
+// mask of an error tile, range[i] the [2] range of every tile but RGB.
+Tensor panel_compose(at::TensorList a, const c10::List<optional<Tensor>>& b, const c10::List<optional<Tensor>>& valid,
+                     const c10::List<optional<Tensor>>& range, at::IntArrayRef kind, at::IntArrayRef row,
+                     at::IntArrayRef col, at::IntArrayRef offset, at::IntArrayRef lut, int64_t rows, int64_t cols,
+                     int64_t H, int64_t W, int64_t F, int64_t t0, int64_t N, int64_t xstar, OptT lut0, OptT lut1,
+                     int64_t layout) {
+  const size_t n = a.size();
+  TORCH_CHECK(n >= 1 && n <= 12, "vda panel_compose: 1 to 12 tiles, got ", n);
+  TORCH_CHECK(b.size() == n && valid.size() == n && range.size() == n && kind.size() == n && row.size() == n &&
+                  col.size() == n && offset.size() == n && lut.size() == n,
+              "vda panel_compose: every per-tile list needs one entry per tile");
+  TORCH_CHECK(rows >= 1 && rows <= 4 && cols >= 1 && cols <= 3, "vda panel_compose: a grid of 1..4 rows by 1..3 columns");
+  TORCH_CHECK(H >= 1 && W >= 1 && rows * H * cols * W < (int64_t(1) << 31),
+              "vda panel_compose: the canvas must hold 1 to 2^31 - 1 pixels");
+  TORCH_CHECK(F >= 1 && F <= 65535, "vda panel_compose: 1 <= F <= 65535 frames per call, got ", F);
+  TORCH_CHECK(N >= 1 && N <= INT32_MAX && t0 >= 0 && t0 + F <= N, "vda panel_compose: 0 <= t0 and t0 + F <= N");
+  TORCH_CHECK(xstar >= 0 && xstar < W, "vda panel_compose: 0 <= xstar < W");
+  TORCH_CHECK(layout >= VDA_VIS_HWC && layout <= VDA_VIS_PLANAR420, "vda panel_compose: unknown layout ", layout);
+  const Tensor& like = a[0];
+  vda_tile tiles[12];
+  for (size_t i = 0; i < n; ++i) {
+    const Tensor& s = a[i];
+    const bool rgb = kind[i] == VDA_TILE_RGB;
+    TORCH_CHECK(kind[i] >= VDA_TILE_RGB && kind[i] <= VDA_TILE_XT, "vda panel_compose: unknown tile kind ", kind[i]);
+    need_contig(s, rgb ? at::kByte : at::kFloat, "a tile source", like);
+    TORCH_CHECK(s.dim() == (rgb ? 4 : 3) && s.size(0) >= 1 && s.size(0) <= INT32_MAX && s.size(1) == H &&
+                    s.size(2) == W && (!rgb || s.size(3) == 3),
+                "vda panel_compose: a tile source must be [n, H, W] float ([n, H, W, 3] uint8 for RGB), got ", s.sizes());
+    TORCH_CHECK(offset[i] >= 0 && offset[i] <= INT32_MAX, "vda panel_compose: a frame offset must be >= 0");
+    vda_tile& t = tiles[i];
+    t = vda_tile{};
+    t.kind = (int32_t)kind[i], t.row = (int32_t)row[i], t.col = (int32_t)col[i];
+    t.offset = (int32_t)offset[i], t.frames = (int32_t)s.size(0), t.lut = (int32_t)lut[i];
+    t.a = s.is_meta() ? nullptr : s.data_ptr();
+    const optional<Tensor> bi = b.get(i), vi = valid.get(i), ri = range.get(i);
+    if (kind[i] == VDA_TILE_ERROR) {
+      TORCH_CHECK(bi.has_value(), "vda panel_compose: an error tile needs its second operand");
+      need_contig(*bi, at::kFloat, "b", like);
+      TORCH_CHECK(bi->sizes() == s.sizes(), "vda panel_compose: b must have a's shape");
+      if (vi) {
+        need_contig(*vi, at::kByte, "valid", like);
+        TORCH_CHECK(vi->sizes() == s.sizes(), "vda panel_compose: valid must have a's shape");
+      }
+      if (!s.is_meta()) {
+        t.b = (const float*)bi->data_ptr();
+        t.valid = vi ? (const uint8_t*)vi->data_ptr() : nullptr;
+      }
+    }
+    if (!rgb) {
+      TORCH_CHECK(ri.has_value(), "vda panel_compose: every tile but RGB needs a range");
+      need_contig(*ri, at::kFloat, "range", like);
+      TORCH_CHECK(ri->numel() == 2, "vda panel_compose: a range must hold (min, max)");
+      TORCH_CHECK(lut[i] == 0 ? lut0.has_value() : (lut[i] == 1 && lut1.has_value()),
+                  "vda panel_compose: a tile names a lut that is missing");
+      if (!s.is_meta()) t.range = (const float*)ri->data_ptr();
+    }
+  }
+  for (const optional<Tensor>* l : {&lut0, &lut1}) {
+    if (!l->has_value()) continue;
+    need_contig(**l, at::kByte, "lut", like);
+    TORCH_CHECK((*l)->dim() == 2 && (*l)->size(0) == 256 && (*l)->size(1) == 3,
+                "vda panel_compose: a lut must be [256, 3]");
+  }
+  const int64_t CH = rows * H, CW = cols * W;
+  const auto opt = like.options().dtype(at::kByte);
+  Tensor out;
+  switch (layout) {
+    case VDA_VIS_HWC: out = at::empty({F, CH, CW, 3}, opt); break;
+    case VDA_VIS_PLANAR444: out = at::empty({F, 3, CH, CW}, opt); break;
+    default: out = at::empty({F, CH * CW + 2 * ((CH + 1) / 2) * ((CW + 1) / 2)}, opt); break;
+  }
+  if (like.is_meta()) return out;
+  const at::OptionalDeviceGuard g(like.device());
+  TORCH_CHECK(out.numel() == vda_panel_compose_bytes((int32_t)F, (int32_t)rows, (int32_t)cols, (int32_t)H, (int32_t)W,
+                                                     (int32_t)layout),
+              "vda panel_compose: output size disagrees with vda_panel_compose_bytes");
+  check_rc(vda_panel_compose(tiles, (int32_t)n, (int32_t)rows, (int32_t)cols, (int32_t)F, (int32_t)t0, (int32_t)N,
+                             (int32_t)H, (int32_t)W, (int32_t)xstar, (const uint8_t*)ptr(lut0),
+                             (const uint8_t*)ptr(lut1), (int32_t)layout, (uint8_t*)out.data_ptr(), stream_of(like)),
+           "vda_panel_compose");
+  return out;
+}
+
 // ---- planar YUV frames -------------------------------------------------------------------------
 // payload [N, frame_stride] uint8 with unit stride along a frame (any base address): the frames' planar bytes.
 int64_t yuv_frame_stride(const Tensor& payload, int64_t h, int64_t w, int64_t chroma, const char* what) {
@@ -800,6 +907,10 @@ TORCH_LIBRARY(vda, m) {
   m.def("preprocess_yuv(Tensor payload, int h, int w, int chroma, int H, int W, float[] mean, float[] std) -> Tensor");
   m.def("depth_range(Tensor depth) -> Tensor");
   m.def("depth_colorize(Tensor depth, Tensor range, Tensor? lut, int layout) -> Tensor");
+  m.def("depth_absdiff_range(Tensor a, Tensor b, Tensor? valid=None) -> Tensor");
+  m.def("panel_compose(Tensor[] a, Tensor?[] b, Tensor?[] valid, Tensor?[] range, int[] kind, int[] row, int[] col, "
+        "int[] offset, int[] lut, int rows, int cols, int H, int W, int F, int t0, int N, int xstar, Tensor? lut0, "
+        "Tensor? lut1, int layout) -> Tensor");
   m.def("gemm(Tensor x, Tensor w, Tensor? bias=None, Tensor? rowbias=None, int rdiv=1, int rmod=1, "
         "Tensor? gamma=None, Tensor? res=None, Tensor? res2=None, int act=0, Tensor? ln_stats=None, "
         "Tensor? ln_colsum=None, int ln_parts=0, float ln_eps=1e-6, Tensor(b!)? stats_out=None, "
@@ -856,6 +967,8 @@ TORCH_LIBRARY(vda, m) {
     m.impl("depth_eval_metrics", &depth_eval_metrics);        \
     m.impl("depth_range", &depth_range);                      \
     m.impl("depth_colorize", &depth_colorize);                \
+    m.impl("depth_absdiff_range", &depth_absdiff_range);      \
+    m.impl("panel_compose", &panel_compose);                  \
     m.impl("yuv_to_rgb", &yuv_to_rgb);                        \
     m.impl("preprocess_yuv", &preprocess_yuv);                \
     m.impl("yuv_downscale", &yuv_downscale);                  \

@@ -368,6 +368,96 @@ def depth_colorize(depth: Tensor, range: Tensor, *, lut: Optional[Tensor] = None
     return _vda().depth_colorize(depth, range, lut, code)
 
 
+TILE_KINDS = {"rgb": _lib.TILE_RGB, "depth": _lib.TILE_DEPTH, "error": _lib.TILE_ERROR, "xt": _lib.TILE_XT}
+
+
+def depth_absdiff_range(a: Tensor, b: Tensor, valid: Optional[Tensor] = None) -> Tensor:
+    """(min, max) of ``valid ? |b - a| : 0`` over two contiguous fp32 GPU tensors of one shape (a = pred,
+    b = gt; ``valid`` bool / uint8 or None) -> [2] fp32 on the device, NaNs skipped, no host sync
+    (vda.h vda_depth_absdiff_range)."""
+    for name, t in (("a", a), ("b", b)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
+            raise ValueError(f"{name} must be a float32 GPU tensor (no CPU path in the product)")
+    if a.numel() < 1 or not a.is_contiguous() or not b.is_contiguous() or b.shape != a.shape or b.device != a.device:
+        raise ValueError(f"a and b must be contiguous, non-empty, of one shape and device, got {tuple(a.shape)} and "
+                         f"{tuple(b.shape)}")
+    if valid is not None:
+        if not isinstance(valid, torch.Tensor) or valid.dtype not in (torch.bool, torch.uint8):
+            raise ValueError("valid must be a bool or uint8 tensor")
+        if valid.shape != a.shape or valid.device != a.device or not valid.is_contiguous():
+            raise ValueError(f"valid must be contiguous with a's shape and device, got {tuple(valid.shape)} on {valid.device}")
+        if valid.dtype == torch.bool:
+            valid = valid.view(torch.uint8)
+    return _vda().depth_absdiff_range(a, b, valid)
+
+
+def panel_compose(tiles, rows: int, cols: int, F: int, t0: int, N: int, xstar: int, *, lut0: Optional[Tensor] = None,
+                  lut1: Optional[Tensor] = None, layout="hwc") -> Tensor:
+    """The canvas frames t0 .. t0 + F - 1 of a comparison video of N frames: ``rows x cols`` tiles of H x W
+    pixels -> uint8 ``"hwc"`` [F, rows*H, cols*W, 3], ``"planar444"`` [F, 3, rows*H, cols*W] or ``"planar420"``
+    [F, CH*CW + 2*ch*cw].  ``tiles``: up to 12 dicts ``kind`` ("rgb" / "depth" / "error" / "xt" or the
+    VDA_TILE_* code), ``row``, ``col``, ``a`` (uint8 [n, H, W, 3] for "rgb", float32 [n, H, W] otherwise) and,
+    optional, ``offset`` (canvas frame t shows source frame t - offset), ``lut`` (0 / 1), ``b`` and ``valid``
+    (an error tile's gt and mask), ``range`` (device [2]; every kind but "rgb").  GPU tensors only
+    (vda.h vda_panel_compose)."""
+    if not isinstance(tiles, (list, tuple)) or not 1 <= len(tiles) <= 12:
+        raise ValueError("tiles must be a list of 1 to 12 tile dicts")
+    code = VIS_LAYOUTS.get(layout, layout) if isinstance(layout, str) else int(layout)
+    if code not in (_lib.VIS_HWC, _lib.VIS_PLANAR444, _lib.VIS_PLANAR420):
+        raise ValueError(f"layout must be one of ['hwc', 'planar420', 'planar444'], got {layout!r}")
+    rows, cols, F, t0, N, xstar = int(rows), int(cols), int(F), int(t0), int(N), int(xstar)
+    if not (1 <= rows <= 4 and 1 <= cols <= 3):
+        raise ValueError(f"the grid must be 1..4 rows by 1..3 columns, got {rows} x {cols}")
+    if not (1 <= F <= 65535 and t0 >= 0 and t0 + F <= N):
+        raise ValueError(f"need 1 <= F <= 65535 and 0 <= t0, t0 + F <= N, got F={F}, t0={t0}, N={N}")
+    dev, H, W, cells = None, None, None, set()
+    a, b, valid, rng, kind, row, col, offset, lut = [], [], [], [], [], [], [], [], []
+    for t in tiles:
+        k = TILE_KINDS.get(t["kind"], t["kind"]) if isinstance(t["kind"], str) else int(t["kind"])
+        if k not in TILE_KINDS.values():
+            raise ValueError(f"tile kind must be one of {sorted(TILE_KINDS)}, got {t['kind']!r}")
+        src = t["a"]
+        want = torch.uint8 if k == _lib.TILE_RGB else torch.float32
+        if not isinstance(src, torch.Tensor) or not src.is_cuda or src.dtype != want or not src.is_contiguous():
+            raise ValueError(f"a tile source must be a contiguous {want} GPU tensor (no CPU path in the product)")
+        if src.dim() != (4 if k == _lib.TILE_RGB else 3) or src.numel() < 1 or (k == _lib.TILE_RGB and src.shape[3] != 3):
+            raise ValueError(f"a tile source must be [n, H, W] ([n, H, W, 3] for rgb), got {tuple(src.shape)}")
+        if dev is None:
+            dev, H, W = src.device, int(src.shape[1]), int(src.shape[2])
+        if src.device != dev or tuple(src.shape[1:3]) != (H, W):
+            raise ValueError(f"every tile must be {H} x {W} on {dev}, got {tuple(src.shape)} on {src.device}")
+        r, c = int(t["row"]), int(t["col"])
+        if not (0 <= r < rows and 0 <= c < cols) or (r, c) in cells:
+            raise ValueError(f"tile cell ({r}, {c}) lies outside the {rows} x {cols} grid or is taken")
+        cells.add((r, c))
+        o, l = int(t.get("offset", 0)), int(t.get("lut", 0))
+        if o < 0 or l not in (0, 1):
+            raise ValueError(f"a tile needs offset >= 0 and lut 0 or 1, got {o} and {l}")
+        tb, tv, tr = t.get("b"), t.get("valid"), t.get("range")
+        if k == _lib.TILE_ERROR:
+            tv = _eval_inputs(src, tb, tv)
+        else:
+            tb = tv = None
+        if k != _lib.TILE_RGB:
+            if not isinstance(tr, torch.Tensor) or tr.dtype != torch.float32 or tr.device != dev or tr.numel() != 2 \
+                    or not tr.is_contiguous():
+                raise ValueError("a tile's range must be a contiguous float32 [2] tensor (min, max) on its device")
+            if (lut0 if l == 0 else lut1) is None:
+                raise ValueError(f"a tile names lut{l}, which is missing")
+        else:
+            tr = None
+        for lst, v in zip((a, b, valid, rng, kind, row, col, offset, lut), (src, tb, tv, tr, k, r, c, o, l)):
+            lst.append(v)
+    if not 0 <= xstar < W:
+        raise ValueError(f"xstar must lie in 0..{W - 1}, got {xstar}")
+    for l in (lut0, lut1):
+        if l is not None and (not isinstance(l, torch.Tensor) or l.dtype != torch.uint8 or l.device != dev
+                              or tuple(l.shape) != (256, 3) or not l.is_contiguous()):
+            raise ValueError("a lut must be a contiguous uint8 [256, 3] tensor on the tiles' device")
+    return _vda().panel_compose(a, b, valid, rng, kind, row, col, offset, lut, rows, cols, H, W, F, t0, N, xstar,
+                                lut0, lut1, code)
+
+
 YUV_CHROMA = {"420": _lib.YUV_420, "422": _lib.YUV_422, "444": _lib.YUV_444, "mono": _lib.YUV_MONO}
 
 

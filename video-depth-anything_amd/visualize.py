@@ -11,6 +11,7 @@ and 1 to 3 bytes per pixel cross to the host instead of 4; see include/vda.h for
 and the stated deviation (NaN / out-of-range indices clamp, numpy's cast is undefined there).
 
 * ``color_table`` - the 256-row RGB or YUV table of a colour map, from ``colorize_depths``' own expressions.
+* ``named_color_table`` - the same for any matplotlib map by name (the comparison video's RdYlGn).
 * ``LibVis`` / ``TorchVis`` - the two backends: libvda kernels, and the same arithmetic in plain torch on any
   device (the orchestration and the CPU tests run on it; it is not a fallback of the product path).
 * ``colorize_depths_device`` - depth tensor -> chunks of uint8 numpy arrays in a file-ready layout.
@@ -38,6 +39,19 @@ def color_table(grayscale: bool = False, spectral: bool = False, yuv: bool = Fal
             table = (matplotlib.colormaps["Spectral"](idx)[..., :3] * 255).astype(np.uint8)
         else:
             table = (np.array(matplotlib.colormaps["inferno"].colors)[idx] * 255).astype(np.uint8)
+    if yuv:
+        table = np.stack(video_io._rgb_to_yuv(table), -1)
+    return np.ascontiguousarray(table, dtype=np.uint8)
+
+
+def named_color_table(name: str, yuv: bool = False) -> np.ndarray:
+    """uint8 [256, 3]: matplotlib's colour map ``name`` (e.g. "RdYlGn") sampled with the expression
+    ``color_table`` uses for Spectral, so ``named_color_table("Spectral")`` is ``color_table(spectral=True)``;
+    ``yuv`` as there."""
+    from . import video_io
+    import matplotlib
+    idx = np.arange(256, dtype=np.uint8)
+    table = (matplotlib.colormaps[name](idx)[..., :3] * 255).astype(np.uint8)
     if yuv:
         table = np.stack(video_io._rgb_to_yuv(table), -1)
     return np.ascontiguousarray(table, dtype=np.uint8)
