@@ -30,7 +30,9 @@ enum {
   VDA_ACT_NONE = 0,
   VDA_ACT_GELU = 1,  /* exact erf GELU (nn.GELU, dinov2.py:61 act_layer)                 */
   VDA_ACT_GEGLU = 2, /* h * gelu(g); weight rows interleaved in 16-row blocks [h|g]      */
-  VDA_ACT_RELU = 3
+  VDA_ACT_RELU = 3,
+  VDA_ACT_SWIGLU = 4 /* h * silu(g) (swiglu_ffn.py: silu(x1) * x2, h = x2, g = x1); rows as GEGLU;
+                        silu(v) = v / (1 + exp(-v)) in fp32, finite for every fp16 pre-activation */
 };
 
 /* Store layouts for vda_gemm. */
@@ -45,8 +47,9 @@ enum {
  *   v = acc + bias[n] + rowbias[((m / rdiv) % rmod) * N + n]
  *   v = act(v)
  *   v = res[m*ldres + n] + res2[m*ldres2 + n] + gamma[n] * v      (each term optional)
- * then stored as fp16.  Null pointers disable a term.  With VDA_ACT_GEGLU the GEMM N counts the
- * interleaved [h|g] weight rows and the output has N/2 columns.
+ * then stored as fp16.  Null pointers disable a term.  With VDA_ACT_GEGLU / VDA_ACT_SWIGLU the GEMM N
+ * counts the interleaved [h|g] weight rows and the output has N/2 columns; every rule stated for GEGLU
+ * below (N % 32 == 0, no rowbias / res2 / pixel shuffle / stats_out, dense only) holds for SwiGLU too.
  */
 typedef struct vda_epilogue {
   const float* bias;     /* [N] or NULL                                                */
@@ -63,7 +66,7 @@ typedef struct vda_epilogue {
   /* LayerNorm folded into the GEMM (block.py:84,87 norm1 / norm2 feeding qkv / fc1): X is the raw
    * row stream x, W holds gamma (.) W_ln, bias holds W_ln beta + b, ln_colsum[n] = sum_k W[n, k] (of the
    * fp16 W actually used), and ln_stats[m] = (mean, rstd) of row m from vda_row_stats.  Then
-   * rstd (x W^T - mean colsum) + bias = LN(x) W_ln^T + b exactly in real arithmetic.  Row store only, no gamma, activation none / gelu.
+   * rstd (x W^T - mean colsum) + bias = LN(x) W_ln^T + b exactly in real arithmetic.  Row store only, no gamma, activation none / gelu / geglu / swiglu.
    * With a rowbias (the motion-module q/k/v: LN(x) + pe[t] then to_q/k/v, motion_module.py:175,256,
    * 263): bias required, no activation / res / res2 / stats_out, rdiv >= 256, N % 256 == 0, 16-byte
    * aligned x, and a shape the GEMM route gives to the phased 256x256 kernel, whose EK 3 epilogue is
@@ -74,7 +77,8 @@ typedef struct vda_epilogue {
    * over ln_parts column blocks (as written through stats_out by the GEMM that produced X); the
    * epilogue forms mean = sum / K, var = max(sumsq / K - mean^2, 0), rstd = 1 / sqrt(var + ln_eps).
    * ln_parts <= 4, M * max(ln_parts, 1) >= 2.  No padding is needed past [M, ln_parts, 2]: the kernels
-   * never read beyond it. */
+   * never read beyond it.  (A row of more than 1024 channels, ViT-g's 1536 = six parts, takes ln_parts = 0
+   * with vda_row_stats passes instead.) */
   int32_t ln_parts;
   float ln_eps;
   /* Producer side: write [M, ceil(N / 256), 2] per-row partial (sum, sum of squares) of the fp16
@@ -129,8 +133,9 @@ const char* vda_last_error(void);
  *   (ls1/ls2 LayerScale + residual); dpt.py:60-68 (projects), dpt.py:70-82 (ConvT k4s4/k2s2);
  *   blocks.py:124-126,160 (out_conv); motion_module.py:119,127 (proj_in/out + residual);
  *   motion_module.py:263,272-273 (to_q/k/v with the PE add :256 folded as a per-frame rowbias);
- *   attention.py:328 (to_out); attention.py:374-384 (GEGLU) and :338 (ff out).
- * Requires K % 8 == 0, ldx % 8 == 0, N % 4 == 0 (N % 32 == 0 for GEGLU).
+ *   attention.py:328 (to_out); attention.py:374-384 (GEGLU) and :338 (ff out);
+ *   dinov2_layers/swiglu_ffn.py (ViT-g: w12 + SwiGLU, w3).
+ * Requires K % 8 == 0, ldx % 8 == 0, N % 4 == 0 (N % 32 == 0 for GEGLU / SwiGLU).
  */
 int vda_gemm(const void* x, int64_t ldx, const void* w, void* y, int64_t ldy,
              int32_t M, int32_t N, int32_t K, const vda_epilogue* epi, void* stream);
@@ -269,7 +274,9 @@ int vda_spatial_attention(const void* qkv, void* out, int32_t B, int32_t N, int3
 /*
  * Temporal self-attention across T <= 32 frames at every spatial site.
  * qkv [(B*T)*S, 3*H*D] half (frame-major rows, [q|k|v] columns, heads contiguous);
- * out [(B*T)*S, H*D] half.  D % 8 == 0, D <= 128.
+ * out [(B*T)*S, H*D] half.  D % 8 == 0, D <= 192 (192 = the ViT-g head's motion modules, C = 1536).
+ * D in {32, 64, 128, 192} with H a multiple of the kernel's waves per block (4, 4, 2, 2) runs a kernel that
+ * stages q, k, v in LDS; every other case one that loads its fragments from HBM directly.
  * rope_theta > 0 applies the rotary embedding of pe='rope' to q and k first: channel pairs
  * (2i, 2i+1) of all C = H*D channels of frame t rotate by t * rope_theta^(-2i/C), in fp32 from the
  * fp16 q/k, rounded back to fp16 (attention.py:403-429, motion_module.py:290-293); 0 = none ('ape',
@@ -621,16 +628,16 @@ int vda_yuv_downscale(const uint8_t* src, int32_t N, int32_t h, int32_t w, int64
  * with fp32 activations AND fp32 weights, fp32 accumulation on the exact-f32 MFMA
  * (v_mfma_f32_16x16x4_f32), exact-erf GELU, expf softmax.  Same layouts and epilogue contract as
  * the fp16 entry points above (vda_epilogue.res / res2 are float here).  Parity tier (i) of
- * SURVEY.md §8(d).  Requirements: K, ldx, N multiples of 4 (GEGLU: N % 32 == 0); conv Cin, Cout
- * multiples of 4; spatial attention D == 64; temporal attention T <= 32, D <= 128.
+ * SURVEY.md §8(d).  Requirements: K, ldx, N multiples of 4 (GEGLU / SwiGLU: N % 32 == 0); conv Cin, Cout
+ * multiples of 4; spatial attention D == 64; temporal attention T <= 32, even D <= 192.
  * vda_gemm_f32 and vda_conv2d_f32 return -22 before any launch for what their kernel does not
  * implement or cannot address (every row access is a float4):
  *   ldx < K; ldy, ldres or ldres2 not a multiple of 4 (res / res2 rows may be strided otherwise);
  *   drop_period != 0 (vda_gemm only: the fp32 kernel stores all M rows);
  *   ln_stats, stats_out, res2_h / res2_w (fp16 entry points only);
  *   a rowbias with rdiv <= 0 or rmod <= 0;
- *   GEMM: VDA_ACT_GEGLU together with a rowbias, a res2 or the pixel-shuffle store (as vda_gemm);
- *   conv: VDA_ACT_GEGLU, the pixel-shuffle store.
+ *   GEMM: VDA_ACT_GEGLU / VDA_ACT_SWIGLU together with a rowbias, a res2 or the pixel-shuffle store (as
+ *   vda_gemm); conv: VDA_ACT_GEGLU / VDA_ACT_SWIGLU, the pixel-shuffle store.
  * sched is ignored (no persistent fp32 kernel).
  */
 int vda_gemm_f32(const float* x, int64_t ldx, const float* w, float* y, int64_t ldy,

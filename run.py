@@ -42,7 +42,7 @@ def add_model_arguments(p):
     p.add_argument("--skip_tmp_block", action="store_true")
     p.add_argument("--input_size", type=int, default=518)
     p.add_argument("--max_res", type=int, default=1280)
-    p.add_argument("--encoder", type=str, default="vitl", choices=["vits", "vitl"])
+    p.add_argument("--encoder", type=str, default="vitl", choices=["vits", "vitb", "vitl", "vitg"])
     p.add_argument("--max_len", type=int, default=-1)
     p.add_argument("--target_fps", type=int, default=-1)
     p.add_argument("--fp32", action="store_true")

@@ -44,7 +44,7 @@ TUNE_EXPORTED = ("vda_debug_force_tile", "vda_debug_gemm_sched", "vda_debug_stri
                  "vda_debug_dconv", "vda_debug_attn")
 TUNE_LIB_PATH = os.path.join(os.path.dirname(_HERE), "build", "tune", "libvda.so")
 
-ACT_NONE, ACT_GELU, ACT_GEGLU, ACT_RELU = 0, 1, 2, 3
+ACT_NONE, ACT_GELU, ACT_GEGLU, ACT_RELU, ACT_SWIGLU = 0, 1, 2, 3, 4
 STORE_ROWS, STORE_PIXEL_SHUFFLE = 0, 1
 VIS_INDEX, VIS_HWC, VIS_PLANAR444, VIS_PLANAR420 = 0, 1, 2, 3  # VDA_VIS_* (vda_depth_colorize layouts)
 TILE_RGB, TILE_DEPTH, TILE_ERROR, TILE_XT = 0, 1, 2, 3  # VDA_TILE_* (vda_panel_compose tile kinds)

@@ -338,7 +338,7 @@ __global__ __launch_bounds__(256, 4) void spatial_attn16_kernel(const h16* __res
 //   Sᵀ[key][q] = Σ_d K[key][d] Q[q][d]       A = K rows, B = Q rows (fragments straight from HBM)
 //   Oᵀ[d][q]   = Σ_key Vᵀ[d][key] Pᵀ[key][q]  B = Pᵀ accumulator registers 8s..8s+7 (k order
 //                16s + 8(j>>2) + 4h + (j&3)), A = Vᵀ by ds_read_b64_tr_b16 from a per-wave V tile.
-// DP = head dim padded to a multiple of 16 (zero-filled), NDT = 32-wide output d tiles.
+// DP = head dim padded to a multiple of 16 (zero-filled, <= 192), NDT = 32-wide output d tiles.
 // =============================================================================================
 // pe='rope' (attention.py:403-429): rotate the 4 channel pairs of an 8-channel q and k fragment of
 // frame t, first channel c0 (even) of C: angle t * theta^(-2i/C) for pair i, fp32 math on the fp16
@@ -569,6 +569,95 @@ __global__ __launch_bounds__(64 * NW) void temporal_attn_lds_kernel(const h16* _
   }
 }
 
+// The staged kernel for D = 192 (ViT-g's motion modules 0 / 1: C = 1536, 8 heads).  A row is 24 16-B chunks, no
+// power of two, so the XOR swizzle above does not apply: rows are padded instead, each tile to the stride its
+// reads want (tools/ta192_stride.py tries every stride against the LDS bank rules):
+//   q, k tiles: 25 chunks (400 B).  A ds_read_b128 lane group is 16 rows of one chunk, rows {0-3, 12-15, 20-27}
+//               (+4, +32): every residue mod 16 once, and an odd stride permutes them over the 16 slots of the
+//               256-B bank row: conflict-free.
+//   v tile:     28 chunks (448 B), the direct kernel's VSTR: a 32-lane group of ds_read_b64_tr_b16 reads 64 B
+//               of 4 consecutive rows, and 448 = 192 (mod 256) lays the four pieces side by side.
+// global_load_lds fills a tile lane-linearly, 64 chunks per instruction, so slot sl is row sl / CS, chunk
+// sl % CS of the padded image; the pad chunks and the rows >= T read the zero page.  13 instructions (12.5
+// used) per q / k tile, 14 per v tile: 13 + 13 + 14 KiB = 40 KiB of LDS per wave for the three tiles (36 KiB
+// of it data), 80 KiB per 2-wave block, two blocks per CU.  The output leaves through the q tile as whole
+// 384-B row segments.  Invariant as above: H % NW == 0.
+template <int NW>
+__global__ __launch_bounds__(64 * NW) void temporal_attn_lds192_kernel(const h16* __restrict__ qkv, h16* __restrict__ out,
+                                                                      int T, int S, int H, float scale_log2,
+                                                                      float rope_theta) {
+  constexpr int D = 192, CH = D / 8;
+  constexpr int CQ = 25, CV = 28;             // chunks per padded row
+  constexpr int SQ = CQ * 8, SV = CV * 8;     // row strides (halfs)
+  constexpr int NIQ = (32 * CQ + 63) / 64, NIV = (32 * CV + 63) / 64;  // DMA instructions per tile
+  constexpr int TQ = NIQ * 512, TV = NIV * 512;                        // halfs per tile: whole instructions
+  constexpr int NST = D / 16, NDT = D / 32;
+  __shared__ __attribute__((aligned(16))) h16 sm[NW * (2 * TQ + TV)];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int b, s, hh;
+  ta_item((long)blockIdx.x * NW + wave, S, H, b, s, hh);
+  const int C = H * D;
+  const long ld = 3L * C;
+  h16* tq = sm + wave * (2 * TQ + TV);
+  h16* tk = tq + TQ;
+  h16* tv = tk + TQ;
+
+#pragma unroll
+  for (int z = 0; z < 3; ++z) {
+    const int cs = z < 2 ? CQ : CV, ni = z < 2 ? NIQ : NIV;
+    h16* base = z == 0 ? tq : z == 1 ? tk : tv;
+#pragma unroll
+    for (int i = 0; i < NIV; ++i) {
+      if (i < ni) {
+        const int sl = i * 64 + lane;
+        const int row = sl / cs, c = sl - row * cs;
+        const void* src = g_ta_zero;
+        if (row < T && c < CH) src = qkv + ((long)(b * T + row) * S + s) * ld + z * C + hh * D + c * 8;
+        __builtin_amdgcn_global_load_lds(src, (VDA_LDS void*)(base + i * 512), 16, 0, 0);
+      }
+    }
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+
+  const int r32 = lane & 31, hf = lane >> 5;
+  f16x acc = {};
+#pragma unroll
+  for (int st = 0; st < NST; ++st) {
+    const int c = st * 2 + hf;
+    h8 kf = *reinterpret_cast<const h8*>(tk + r32 * SQ + c * 8);
+    h8 qf = *reinterpret_cast<const h8*>(tq + r32 * SQ + c * 8);
+    if (rope_theta > 0.f) rope_frag(qf, kf, r32, hh * D + c * 8, C, rope_theta);
+    acc = mfma32(kf, qf, acc);
+  }
+  h8 pf[2];
+  const float inv = ta_softmax(acc, T, hf, scale_log2, pf);
+
+#pragma unroll
+  for (int dt = 0; dt < NDT; ++dt) {
+    f16x o = {};
+#pragma unroll
+    for (int st = 0; st < 2; ++st) {
+      int r0, col;
+      ta_vpos(lane, dt, st, r0, col);
+      o = mfma32(vt_frag(tv + r0 * SV + col, tv + (r0 + 8) * SV + col), pf[st], o);
+    }
+#pragma unroll
+    for (int gq = 0; gq < 4; ++gq) {  // into the q tile (its fragments are consumed), as rows
+      const int d = o_chan(dt, gq, hf);
+      *reinterpret_cast<h4*>(tq + r32 * SQ + d) = o_group(o, gq, inv);
+    }
+  }
+  __builtin_amdgcn_wave_barrier();  // the row reads below follow the other lanes' writes (one wave: LDS is in order)
+#pragma unroll
+  for (int i = 0; i < 32 * CH / 64; ++i) {
+    const int sl = i * 64 + lane;
+    const int row = sl / CH, c = sl - row * CH;
+    const uint4 v = *reinterpret_cast<const uint4*>(tq + row * SQ + c * 8);
+    if (row < T) *reinterpret_cast<uint4*>(out + ((long)(b * T + row) * S + s) * C + hh * D + c * 8) = v;
+  }
+}
+
 // vda_debug_attn (tuning build): 1 = the direct-load temporal kernel for every head dim
 VDA_KNOB(int, g_ta_direct, 0);
 
@@ -600,13 +689,13 @@ extern "C" int vda_temporal_attention(const void* qkv, void* out, int32_t B, int
   VDA_CHECK_ARG(qkv && out, "null pointer");
   VDA_CHECK_ARG(B > 0 && S > 0 && H > 0, "empty attention");
   VDA_CHECK_ARG(T > 0 && T <= 32, "temporal attention needs 1 <= T <= 32 (PE table length)");
-  VDA_CHECK_ARG(D > 0 && D % 8 == 0 && D <= 128, "head dim must be a multiple of 8, <= 128");
+  VDA_CHECK_ARG(D > 0 && D % 8 == 0 && D <= 192, "head dim must be a multiple of 8, <= 192");
   const long items = (long)B * S * H;
   dim3 grid((unsigned)((items + VDA_TA_NW - 1) / VDA_TA_NW));
   hipStream_t st = (hipStream_t)stream;
   const float sl = scale * 1.4426950408889634f;
   // q / k / v rows staged in LDS for the head dims the model uses (128 at C = 1024, 32 at C = 256, 8
-  // heads); the direct-load kernel below serves the other head dims
+  // heads); the direct-load kernel below serves the other head dims (every D % 8 == 0 up to 192)
   if (!g_ta_direct && (D == 32 || D == 64 || D == 128)) {
     const int nw = D == 128 ? 2 : 4;  // 24 / 12 / 6 KiB of LDS per wave
     if (H % nw == 0) {  // the LDS kernel's invariant: no idle wave
@@ -624,6 +713,14 @@ extern "C" int vda_temporal_attention(const void* qkv, void* out, int32_t B, int
       return 0;
     }
   }
+  // D = 192 (ViT-g's C = 1536): staged too, by measurement (32 x 1,369 sites, 8 heads: 118.7 us = 4.5 TB/s against
+  // the direct-load kernel's 171.0, profiles/vitg_temporal_d192.log); 40 KiB of LDS per wave, 2 waves per block
+  if (!g_ta_direct && D == 192 && H % 2 == 0) {
+    hipLaunchKernelGGL((temporal_attn_lds192_kernel<2>), dim3((unsigned)(items / 2)), dim3(128), 0, st, (const h16*)qkv,
+                       (h16*)out, T, S, H, sl, rope_theta);
+    VDA_LAUNCH_CHECK();
+    return 0;
+  }
   const int dp = (D + 15) / 16 * 16;
 #define VDA_TA(DPV) hipLaunchKernelGGL(temporal_attn_kernel<DPV>, grid, dim3(64 * VDA_TA_NW), 0, st, (const h16*)qkv, (h16*)out, B, T, S, H, D, sl, rope_theta)
   switch (dp) {
@@ -634,7 +731,12 @@ extern "C" int vda_temporal_attention(const void* qkv, void* out, int32_t B, int
     case 80: VDA_TA(80); break;
     case 96: VDA_TA(96); break;
     case 112: VDA_TA(112); break;
-    default: VDA_TA(128); break;
+    case 128: VDA_TA(128); break;
+    // D 136 .. 192 (ViT-g's motion modules 0 / 1: C = 1536, 8 heads): the V tile is 4 x 32 x 224 halfs = 56 KiB
+    case 144: VDA_TA(144); break;
+    case 160: VDA_TA(160); break;
+    case 176: VDA_TA(176); break;
+    default: VDA_TA(192); break;
   }
 #undef VDA_TA
   VDA_LAUNCH_CHECK();

@@ -148,6 +148,17 @@ __device__ __forceinline__ float gelu_erf(float x) {
   return 0.5f * x * (1.0f + erf_fast(x * 0.70710678118654752f));
 }
 
+// SiLU gate of VDA_ACT_SWIGLU on an fp32 accumulator: v / (1 + exp(-v)) as one v_exp_f32, one add, one
+// v_rcp_f32 and one multiply.  exp(-v) overflows to +inf for v < -88.7, 1 / inf = 0 and v * 0 = -0; for
+// large v it underflows to 0 and the result is v: finite for every finite v (the exp(v) / (1 + exp(v)) form
+// is inf / inf = NaN above 88.7).
+__device__ __forceinline__ float silu_f32(float v) {
+  return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(v * -1.4426950408889634f));
+}
+// The gated activations (vda.h: VDA_ACT_GEGLU = 2, VDA_ACT_SWIGLU = 4): interleaved [h | g] weight rows,
+// N / 2 output columns
+__host__ __device__ constexpr bool vda_glu(int act) { return act == 2 || act == 4; }
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -18,6 +18,8 @@
 //   layernorm / groupnorm / upsample / im2col / depth tail: fp32 versions of the fp16 kernels.
 #include "vda_common.h"
 #include "../../include/vda.h"
+static_assert(vda_glu(VDA_ACT_GEGLU) && vda_glu(VDA_ACT_SWIGLU) && !vda_glu(VDA_ACT_GELU) && !vda_glu(VDA_ACT_RELU),
+              "vda_glu (vda_common.h) names the gated activation codes of vda.h");
 #include <cmath>
 
 namespace {
@@ -39,6 +41,8 @@ __device__ __forceinline__ f4 mfma_f32(float a, float b, f4 c) {
 }
 
 __device__ __forceinline__ float gelu_exact(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f)); }
+// SiLU gate of VDA_ACT_SWIGLU: expf(-v) = +inf for v < -88.7 gives v / inf = -0, never inf / inf
+__device__ __forceinline__ float silu_exact(float v) { return v / (1.0f + expf(-v)); }
 
 template <bool CONV>
 __device__ __forceinline__ f4 load_x4(const F32Params& p, int m, int k, int bt, int oy, int ox) {
@@ -161,7 +165,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(F32Params p, int tiles_n)
   for (int j = 0; j < 4; ++j) {
     const int m = m0 + wm * 64 + j * 16 + fr;
     if (m >= p.M) continue;
-    if constexpr (ACT == VDA_ACT_GEGLU) {
+    if constexpr (vda_glu(ACT)) {
 #pragma unroll
       for (int pr = 0; pr < 2; ++pr) {
         const int nb = n0 + wn * 64 + pr * 32;  // 32-row [h16 | g16] block
@@ -175,7 +179,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(F32Params p, int tiles_n)
         }
         f4 v;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = vh[q] * gelu_exact(vg[q]);
+        for (int q = 0; q < 4; ++q) v[q] = vh[q] * (ACT == VDA_ACT_SWIGLU ? silu_exact(vg[q]) : gelu_exact(vg[q]));
         if (e.gamma) v *= *reinterpret_cast<const f4*>(e.gamma + nout);
         if (e.res) v += *reinterpret_cast<const f4*>((const float*)e.res + (long)m * e.ldres + nout);
         *reinterpret_cast<f4*>(p.y + (long)m * p.ldy + nout) = v;
@@ -292,13 +296,16 @@ __global__ __launch_bounds__(256) void spatial_attn_f32_kernel(const float* __re
 }
 
 // ---- temporal attention (fp32) ----------------------------------------------------------------
-// One wave per (b, site, head); lane t < T is query frame t.  qkv rows (b*T + t)*S + s.
+// One wave per (b, site, head); lane t < T is query frame t.  qkv rows (b*T + t)*S + s.  DM: the largest
+// head dim of the instantiation (128: 49 KiB of LDS; 192, ViT-g's D at C = 1536: 73 KiB).
+template <int DM>
 __global__ __launch_bounds__(64) void temporal_attn_f32_kernel(const float* __restrict__ qkv, float* __restrict__ out,
                                                                int T, int S, int H, int D, float scale,
                                                                float rope_theta) {
-  __shared__ float qt[128 * 33];  // Q^T [d][t] (row 33 floats)
-  __shared__ float kk[32 * 129];  // K [t][d]
-  __shared__ float vv[32 * 129];  // V [t][d]
+  constexpr int RS = DM + 1;      // K / V row stride (floats)
+  __shared__ float qt[DM * 33];   // Q^T [d][t] (row 33 floats)
+  __shared__ float kk[32 * RS];   // K [t][d]
+  __shared__ float vv[32 * RS];   // V [t][d]
   const int lane = threadIdx.x;
   const int h = blockIdx.x % H;
   const int site = blockIdx.x / H;  // b * S + s
@@ -323,10 +330,10 @@ __global__ __launch_bounds__(64) void temporal_attn_f32_kernel(const float* __re
     }
     qt[d * 33 + t] = qa;
     qt[(d + 1) * 33 + t] = qb;
-    kk[t * 129 + d] = ka;
-    kk[t * 129 + d + 1] = kb;
-    vv[t * 129 + d] = row[2 * C];
-    vv[t * 129 + d + 1] = row[2 * C + 1];
+    kk[t * RS + d] = ka;
+    kk[t * RS + d + 1] = kb;
+    vv[t * RS + d] = row[2 * C];
+    vv[t * RS + d + 1] = row[2 * C + 1];
   }
   __syncthreads();
   if (lane >= T) return;
@@ -337,7 +344,7 @@ __global__ __launch_bounds__(64) void temporal_attn_f32_kernel(const float* __re
     const float qd = qt[d * 33 + lane];
 #pragma unroll
     for (int j = 0; j < 32; ++j)
-      if (j < T) sc[j] = fmaf(qd, kk[j * 129 + d], sc[j]);
+      if (j < T) sc[j] = fmaf(qd, kk[j * RS + d], sc[j]);
   }
   float mx = -INFINITY;
 #pragma unroll
@@ -355,7 +362,7 @@ __global__ __launch_bounds__(64) void temporal_attn_f32_kernel(const float* __re
     float a = 0.f;
 #pragma unroll
     for (int j = 0; j < 32; ++j)
-      if (j < T) a = fmaf(sc[j], vv[j * 129 + d], a);
+      if (j < T) a = fmaf(sc[j], vv[j * RS + d], a);
     orow[d] = a;
   }
 }
@@ -502,6 +509,10 @@ int launch_f32(const F32Params& p, hipStream_t st) {
       if (CONV) return vda_set_error(-22, "GEGLU epilogue is dense-only");
       hipLaunchKernelGGL((gemm_f32_kernel<CONV, VDA_ACT_GEGLU>), g, bl, 0, st, p, tiles_n);
       break;
+    case VDA_ACT_SWIGLU:  // dense only, as GEGLU (vda_conv2d_f32 refuses both): no conv kernel is built for it
+      if constexpr (CONV) return vda_set_error(-22, "GEGLU epilogue is dense-only");
+      else hipLaunchKernelGGL((gemm_f32_kernel<CONV, VDA_ACT_SWIGLU>), g, bl, 0, st, p, tiles_n);
+      break;
     default: return vda_set_error(-22, "unknown activation");
   }
   VDA_LAUNCH_CHECK();
@@ -522,8 +533,8 @@ extern "C" int vda_gemm_f32(const float* x, int64_t ldx, const float* w, float* 
   VDA_CHECK_ARG(!epi->res2 || epi->ldres2 % 4 == 0, "fp32 GEMM needs ldres2 a multiple of 4");
   // the kernel stores all M rows: the cls-row drop exists on vda_gemm's phased route only
   VDA_CHECK_ARG(epi->drop_period == 0, "fp32 GEMM: no drop_period (vda_gemm only)");
-  // the GEGLU branch of the kernel applies bias, gamma and res, and stores rows
-  VDA_CHECK_ARG(epi->act != VDA_ACT_GEGLU || (N % 32 == 0 && !epi->rowbias && !epi->res2 &&
+  // the GEGLU / SwiGLU branch of the kernel applies bias, gamma and res, and stores rows
+  VDA_CHECK_ARG(!vda_glu(epi->act) || (N % 32 == 0 && !epi->rowbias && !epi->res2 &&
                                               epi->store == VDA_STORE_ROWS),
                 "GEGLU needs N % 32 == 0, no rowbias/res2, row store");
   VDA_CHECK_ARG(epi->store != VDA_STORE_PIXEL_SHUFFLE || (epi->ps_k > 0 && epi->ps_cout % 4 == 0 &&
@@ -545,7 +556,7 @@ extern "C" int vda_conv2d_f32(const float* x, const float* w, float* y, int32_t 
   VDA_CHECK_ARG(x && w && y && epi, "null pointer");
   VDA_CHECK_ARG(BT > 0 && H > 0 && W > 0 && ks > 0 && stride > 0 && pad >= 0, "bad conv geometry");
   VDA_CHECK_ARG(Cin % 4 == 0 && Cout % 4 == 0, "fp32 conv needs Cin, Cout multiples of 4");
-  VDA_CHECK_ARG(epi->act != VDA_ACT_GEGLU && epi->store == VDA_STORE_ROWS, "conv epilogue: no GEGLU / pixel shuffle");
+  VDA_CHECK_ARG(!vda_glu(epi->act) && epi->store == VDA_STORE_ROWS, "conv epilogue: no GEGLU / pixel shuffle");
   VDA_CHECK_ARG(epi->res2_h == 0 && epi->res2_w == 0, "fp32 conv: no upsampled res2 (materialise it)");
   VDA_CHECK_ARG(!epi->bias9, "fp32 conv: no bias9");
   VDA_CHECK_ARG(!epi->rowbias || (epi->rdiv > 0 && epi->rmod > 0), "rowbias needs rdiv, rmod > 0");
@@ -581,11 +592,15 @@ extern "C" int vda_temporal_attention_f32(const float* qkv, float* out, int32_t 
                                           int32_t D, float scale, float rope_theta, void* stream) {
   VDA_CHECK_ARG(qkv && out, "null pointer");
   VDA_CHECK_ARG(B > 0 && T > 0 && S > 0 && H > 0 && D > 0, "empty attention");
-  VDA_CHECK_ARG(T <= 32 && D <= 128 && D % 2 == 0, "temporal attention: T <= 32, even D <= 128");
+  VDA_CHECK_ARG(T <= 32 && D <= 192 && D % 2 == 0, "temporal attention: T <= 32, even D <= 192");
   const long blocks = (long)B * S * H;
   VDA_CHECK_ARG(blocks < 0x7fffffffL, "grid too large");
-  hipLaunchKernelGGL(temporal_attn_f32_kernel, dim3((unsigned)blocks), dim3(64), 0, (hipStream_t)stream, qkv, out, T, S,
-                     H, D, scale, rope_theta);
+  if (D <= 128)
+    hipLaunchKernelGGL(temporal_attn_f32_kernel<128>, dim3((unsigned)blocks), dim3(64), 0, (hipStream_t)stream, qkv, out,
+                       T, S, H, D, scale, rope_theta);
+  else
+    hipLaunchKernelGGL(temporal_attn_f32_kernel<192>, dim3((unsigned)blocks), dim3(64), 0, (hipStream_t)stream, qkv, out,
+                       T, S, H, D, scale, rope_theta);
   VDA_LAUNCH_CHECK();
   return 0;
 }

@@ -56,7 +56,8 @@ struct GemmRoute {
 // each epilogue pointer is set and at alignments; never at what a pointer points to.
 GemmRoute gemm_route(const GemmParams& p, bool conv) {
   const vda_epilogue& e = p.epi;
-  const bool plain = e.act == VDA_ACT_NONE, gelu = e.act == VDA_ACT_GELU, geglu = e.act == VDA_ACT_GEGLU;
+  const bool plain = e.act == VDA_ACT_NONE, gelu = e.act == VDA_ACT_GELU;
+  const bool geglu = vda_glu(e.act);  // GEGLU and SwiGLU take the same routes: they differ in the gate alone
   GemmRoute r{g_force_tile, PH_STAGED, false};
   if (r.cfg < 0) {
     // measured on MI355X (tools/archive/bench_gemm.py): 256x256 wins every large-N shape; N = 128 prefers
@@ -133,7 +134,7 @@ void launch_phased(Phased v, const GemmParams& p, hipStream_t st) {
   auto go = [&](void (*kernel)(GemmParams, int, int)) {
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(512), 0, st, p, tiles_m, tiles_n);
   };
-  constexpr bool PLAIN = ACT == VDA_ACT_NONE, GELU = ACT == VDA_ACT_GELU, GEGLU = ACT == VDA_ACT_GEGLU;
+  constexpr bool PLAIN = ACT == VDA_ACT_NONE, GELU = ACT == VDA_ACT_GELU, GEGLU = vda_glu(ACT);
   constexpr bool D256 = !CONV && XR == 2;
   if constexpr (!CONV && PLAIN)
     if (v == PH_ROWB) return go(gemm256_kernel<XR, WR, CONV, ACT, true>);
@@ -176,9 +177,12 @@ int launch(const GemmParams& p, hipStream_t st) {
   int rc = 0;
   switch (p.epi.act) {
     case VDA_ACT_GELU:
-    case VDA_ACT_GEGLU:  // vda_conv2d admits none / ReLU only: no conv kernel is built for these
+    case VDA_ACT_GEGLU:
+    case VDA_ACT_SWIGLU:  // vda_conv2d admits none / ReLU only: no conv kernel is built for these
       if constexpr (CONV) return vda_set_error(-22, "conv epilogue: activation none / relu");
-      else rc = p.epi.act == VDA_ACT_GELU ? launch_cfg<CONV, VDA_ACT_GELU>(r, p, st) : launch_cfg<CONV, VDA_ACT_GEGLU>(r, p, st);
+      else rc = p.epi.act == VDA_ACT_GELU    ? launch_cfg<CONV, VDA_ACT_GELU>(r, p, st)
+                : p.epi.act == VDA_ACT_GEGLU ? launch_cfg<CONV, VDA_ACT_GEGLU>(r, p, st)
+                                             : launch_cfg<CONV, VDA_ACT_SWIGLU>(r, p, st);
       break;
     case VDA_ACT_RELU: rc = launch_cfg<CONV, VDA_ACT_RELU>(r, p, st); break;
     default: rc = launch_cfg<CONV, VDA_ACT_NONE>(r, p, st); break;
@@ -255,18 +259,18 @@ vda_epilogue vda_default_epi() {
 
 int vda_check_epi(const vda_epilogue& e, int M, int N) {
   VDA_CHECK_ARG(!e.rowbias || (e.rdiv > 0 && e.rmod > 0), "rowbias needs rdiv, rmod > 0");
-  VDA_CHECK_ARG(e.act >= 0 && e.act <= 3, "unknown activation");
-  VDA_CHECK_ARG(e.act != VDA_ACT_GEGLU || (N % 32 == 0 && !e.rowbias && e.store == 0 && !e.res2),
+  VDA_CHECK_ARG(e.act >= 0 && e.act <= 4, "unknown activation");
+  VDA_CHECK_ARG(!vda_glu(e.act) || (N % 32 == 0 && !e.rowbias && e.store == 0 && !e.res2),
                 "GEGLU needs N % 32 == 0, no rowbias/res2, row store");
   VDA_CHECK_ARG(e.store == VDA_STORE_ROWS ||
                 (e.store == VDA_STORE_PIXEL_SHUFFLE && e.ps_k > 0 && e.ps_cout > 0 && e.ps_cout % 4 == 0 &&
                  e.ps_hin > 0 && e.ps_win > 0 && N == e.ps_k * e.ps_k * e.ps_cout && !e.res && !e.res2),
                 "bad pixel-shuffle store geometry");
-  // the LN fold exists for the activation-free, GELU and GEGLU epilogues (every kernel route applies it
+  // the LN fold exists for the activation-free, GELU, GEGLU and SwiGLU epilogues (every kernel route applies it
   // there; anything else would silently run an un-normalised GEMM); with a row bias only on the
   // phased route's EK 3 epilogue (vda_gemm checks the route)
   VDA_CHECK_ARG(!e.ln_stats || (e.ln_colsum && e.store == VDA_STORE_ROWS && !e.gamma &&
-                                 (e.act == VDA_ACT_NONE || e.act == VDA_ACT_GELU || e.act == VDA_ACT_GEGLU)),
+                                 (e.act == VDA_ACT_NONE || e.act == VDA_ACT_GELU || vda_glu(e.act))),
                 "ln_stats needs ln_colsum, a row store, no gamma, activation none / gelu / geglu");
   VDA_CHECK_ARG(!e.ln_stats || !e.rowbias ||
                     (e.act == VDA_ACT_NONE && e.bias && !e.res && !e.res2 && !e.stats_out && e.rdiv >= 256),
@@ -275,7 +279,7 @@ int vda_check_epi(const vda_epilogue& e, int M, int N) {
   // the phased route stages the statistics in 16-byte pieces, reading the last one 8 B early when the
   // float count is not a multiple of 4: the buffer must hold at least one whole piece (M * P >= 2)
   VDA_CHECK_ARG(!e.ln_stats || (long)M * (e.ln_parts > 0 ? e.ln_parts : 1) >= 2, "ln_stats needs M * max(ln_parts, 1) >= 2");
-  VDA_CHECK_ARG(!e.stats_out || (e.store == VDA_STORE_ROWS && e.act != VDA_ACT_GEGLU),
+  VDA_CHECK_ARG(!e.stats_out || (e.store == VDA_STORE_ROWS && !vda_glu(e.act)),
                 "stats_out needs a row store and no GEGLU");
   VDA_CHECK_ARG(!e.res || e.ldres % 4 == 0, "ldres % 4");
   VDA_CHECK_ARG(!e.res2 || e.ldres2 % 4 == 0, "ldres2 % 4");

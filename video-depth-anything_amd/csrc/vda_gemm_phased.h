@@ -195,7 +195,7 @@ __device__ __forceinline__ void stat_acc(h8 t, float& s, float& q) {
 // operations a tile issues after it has pre-issued the next tile's prologue DMA.
 template <int XR, int WR, int ACT>
 constexpr int phased_nit() {
-  constexpr int OW = (ACT == VDA_ACT_GEGLU) ? 64 * WR : 128 * WR;
+  constexpr int OW = (vda_glu(ACT)) ? 64 * WR : 128 * WR;
   return (128 * XR) / (512 / (OW / 8));
 }
 
@@ -241,7 +241,7 @@ __device__ __forceinline__ int gemm256_tile(const GemmParams& p, int vb, int til
   // pixel runs at remapped addresses (phase 2 below), instead of 8-byte scatter stores per element
   // (WR == 2: a 256-wide N tile, 16 rows per store iteration, the only shape ps_store is compiled for; the
   // 16-B row-run stores need a 16-B aligned y)
-  const bool ps_rows = !EK && ACT != VDA_ACT_GEGLU && !ROWB && XR == 2 && WR == 2 &&
+  const bool ps_rows = !EK && !vda_glu(ACT) && !ROWB && XR == 2 && WR == 2 &&
                        p.epi.store == VDA_STORE_PIXEL_SHUFFLE && p.epi.ps_cout % 256 == 0 && p.epi.ps_win >= 16 &&
                        (long)p.M * p.N * 2 < 0x7fffffffL && (uintptr_t)p.y % 16 == 0;
   const bool rows_store = (EK || SUBP) ? true : (p.epi.store == VDA_STORE_ROWS || ps_rows);
@@ -534,11 +534,11 @@ __device__ __forceinline__ int gemm256_tile(const GemmParams& p, int vb, int til
       const int nc = n < p.N ? n : 0;
       pbv[i] = f4{0.f, 0.f, 0.f, 0.f};
       pgv[i] = f4{1.f, 1.f, 1.f, 1.f};
-      if (has_bias) pbv[i] = *reinterpret_cast<const f4*>(e.bias + (ACT == VDA_ACT_GEGLU ? (n0 + wn * 64 + (i & ~1) * 16 + nq0 < p.N ? n0 + wn * 64 + (i & ~1) * 16 + nq0 : 0) + (i & 1) * 16 : nc));
+      if (has_bias) pbv[i] = *reinterpret_cast<const f4*>(e.bias + (vda_glu(ACT) ? (n0 + wn * 64 + (i & ~1) * 16 + nq0 < p.N ? n0 + wn * 64 + (i & ~1) * 16 + nq0 : 0) + (i & 1) * 16 : nc));
       if constexpr (LNF) {
         pgv[i] = *reinterpret_cast<const f4*>(e.ln_colsum + nc);  // sum_k W[n, k] (LN fold)
       } else if (has_gamma) {
-        if constexpr (ACT == VDA_ACT_GEGLU) {
+        if constexpr (vda_glu(ACT)) {
           if (i % 2 == 0) pgv[i] = *reinterpret_cast<const f4*>(e.gamma + (n < p.N ? (n0 >> 1) + ((wn * 64 + i * 16) >> 1) + nq0 : 0));
         } else {
           pgv[i] = *reinterpret_cast<const f4*>(e.gamma + nc);
@@ -744,7 +744,7 @@ __device__ __forceinline__ int gemm256_tile(const GemmParams& p, int vb, int til
     // [256][OW] image (8-byte units XOR-swizzled by row&15: conflict-free both ways); phase 2 reads
     // it back as whole rows, adds the residual(s) with 16-byte loads and stores 16-byte chunks, so
     // every output row is written by full contiguous 128-B lines.
-    constexpr int OW = (ACT == VDA_ACT_GEGLU) ? BN / 2 : BN;  // output columns of this tile
+    constexpr int OW = (vda_glu(ACT)) ? BN / 2 : BN;  // output columns of this tile
     __syncthreads();                                         // all waves done with the operand image
     const vda_epilogue& e = p.epi;
     // Per-channel operands are loaded ONCE per lane, unconditionally from clamped addresses, before
@@ -790,13 +790,13 @@ __device__ __forceinline__ int gemm256_tile(const GemmParams& p, int vb, int til
       f4 bv[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i)
-        bv[i] = PREF ? pbv[i] : *reinterpret_cast<const f4*>(e.bias + (ACT == VDA_ACT_GEGLU ? ncl[i & ~1] + (i & 1) * 16 : ncl[i]));
+        bv[i] = PREF ? pbv[i] : *reinterpret_cast<const f4*>(e.bias + (vda_glu(ACT) ? ncl[i & ~1] + (i & 1) * 16 : ncl[i]));
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 8; ++j) acc[i][j] += bv[i];
     }
-    if constexpr (ACT != VDA_ACT_GEGLU && ROWB) {
+    if constexpr (!vda_glu(ACT) && ROWB) {
       if (e.rowbias) {  // per-row bias (folded positional terms): 4 loads per output row group
         // (m / rdiv) % rmod by fp32 reciprocals + one integer correction each (m < 2^24: exact)
         const float inv_div = 1.f / (float)e.rdiv, inv_mod = 1.f / (float)e.rmod;
@@ -866,7 +866,7 @@ __device__ __forceinline__ int gemm256_tile(const GemmParams& p, int vb, int til
       // values per step: all 16 LDS reads are issued before the first is consumed (one wait per group
       // instead of one per value)
 #pragma unroll
-      for (int i = (ACT == VDA_ACT_GEGLU ? 1 : 0); i < 4; i += (ACT == VDA_ACT_GEGLU ? 2 : 1))
+      for (int i = (vda_glu(ACT) ? 1 : 0); i < 4; i += (vda_glu(ACT) ? 2 : 1))
 #pragma unroll
         for (int j = 0; j < 8; j += 4) {
           phi_f2 ab[16];
@@ -882,22 +882,23 @@ __device__ __forceinline__ int gemm256_tile(const GemmParams& p, int vb, int til
     auto phase1 = [&](auto g_tag) {
       constexpr bool HG = decltype(g_tag)::value;
 #pragma unroll
-      for (int i = 0; i < 4; i += (ACT == VDA_ACT_GEGLU ? 2 : 1)) {
+      for (int i = 0; i < 4; i += (vda_glu(ACT) ? 2 : 1)) {
         const int nl = wn * 64 + i * 16 + nq;  // local W row of this lane's first channel
         f4 gv = f4{1.f, 1.f, 1.f, 1.f};
         if constexpr (HG) {
           if constexpr (PREF) gv = pgv[i];
-          else gv = *reinterpret_cast<const f4*>(e.gamma + (ACT == VDA_ACT_GEGLU ? (nok[i] ? (n0 >> 1) + ((wn * 64 + i * 16) >> 1) + nq : 0) : ncl[i]));
+          else gv = *reinterpret_cast<const f4*>(e.gamma + (vda_glu(ACT) ? (nok[i] ? (n0 >> 1) + ((wn * 64 + i * 16) >> 1) + nq : 0) : ncl[i]));
         }
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const int ml = wm * 128 + j * 16 + mcol;
           f4 v;
           int col;
-          if constexpr (ACT == VDA_ACT_GEGLU) {
+          if constexpr (vda_glu(ACT)) {
             const f4 vh = acc[i][j], vg = acc[i + 1][j];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = vh[r] * (TAB ? vg[r] : gelu_erf(vg[r]));  // TAB: gate done above
+            for (int r = 0; r < 4; ++r)  // TAB: gate done above
+              v[r] = vh[r] * (TAB ? vg[r] : ACT == VDA_ACT_SWIGLU ? silu_f32(vg[r]) : gelu_erf(vg[r]));
             col = ((wn * 64 + i * 16) >> 1) + nq;
           } else {
             v = acc[i][j];
@@ -919,8 +920,8 @@ __device__ __forceinline__ int gemm256_tile(const GemmParams& p, int vb, int til
         }
       }
     };
-    const int nout = (ACT == VDA_ACT_GEGLU) ? (p.N >> 1) : p.N;
-    const int cout0 = (ACT == VDA_ACT_GEGLU) ? (n0 >> 1) : n0;
+    const int nout = (vda_glu(ACT)) ? (p.N >> 1) : p.N;
+    const int cout0 = (vda_glu(ACT)) ? (n0 >> 1) : n0;
     // Phase 2: thread -> fixed (row0 + RPI * it, 16-byte chunk q).  Every iteration reuses the same
     // LDS swizzle and advances both addresses by constants; stores (and residual loads) are buffer
     // ops whose range check drops rows >= M and chunks >= nout (offset 0x80000000), so the loop
@@ -1046,7 +1047,7 @@ __device__ __forceinline__ int gemm256_tile(const GemmParams& p, int vb, int til
     // co0 + 255 of output pixel (yh k + ki, xw k + kj); the row walk advances (xw, yh, bt) incrementally
     // (RPI = 16 rows per step, ps_win >= 16: at most one wrap)
     auto ps_store = [&]() {
-      if constexpr (RPI == 16 && ACT != VDA_ACT_GEGLU && !ROWB && XR == 2) {  // the instantiations ps_rows admits
+      if constexpr (RPI == 16 && !vda_glu(ACT) && !ROWB && XR == 2) {  // the instantiations ps_rows admits
       const int k = e.ps_k, cout = e.ps_cout, win = e.ps_win, hin = e.ps_hin;
       const int ij = n0 / cout, co0 = n0 - ij * cout, ki = ij / k, kj = ij - ki * k;
       const __amdgpu_buffer_rsrc_t rz =
@@ -1135,7 +1136,7 @@ __device__ __forceinline__ int gemm256_tile(const GemmParams& p, int vb, int til
   }
   if constexpr (EK != 0) {
     return succ;  // row store only
-  } else if constexpr (ACT == VDA_ACT_GEGLU) {
+  } else if constexpr (vda_glu(ACT)) {
 #pragma unroll
     for (int i = 0; i < 4; i += 2) {
       const int nbase = n0 + wn * 64 + i * 16;
@@ -1144,7 +1145,7 @@ __device__ __forceinline__ int gemm256_tile(const GemmParams& p, int vb, int til
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const int m = m0 + wm * 128 + j * 16 + mcol;
-        if (m < p.M) epi_geglu4(p, m, nbase + nq, nbase + 16 + nq, n_out, acc[i][j], acc[i + 1][j]);
+        if (m < p.M) epi_geglu4<ACT>(p, m, nbase + nq, nbase + 16 + nq, n_out, acc[i][j], acc[i + 1][j]);
       }
     }
   } else {

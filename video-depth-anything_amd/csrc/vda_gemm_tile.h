@@ -172,7 +172,8 @@ __device__ __forceinline__ void epi_store4(const GemmParams& p, int m, int n, f4
   *reinterpret_cast<h4*>(p.y + off) = o;
 }
 
-// GEGLU: h and g accumulators for the same 4 output channels.  Output column = n_out.
+// GEGLU / SwiGLU (ACT): h and g accumulators for the same 4 output channels.  Output column = n_out.
+template <int ACT>
 __device__ __forceinline__ void epi_geglu4(const GemmParams& p, int m, int nh, int ng, int n_out,
                                            f4 vh, f4 vg) {
   const vda_epilogue& e = p.epi;
@@ -191,7 +192,7 @@ __device__ __forceinline__ void epi_geglu4(const GemmParams& p, int m, int nh, i
   }
   f4 v;
 #pragma unroll
-  for (int j = 0; j < 4; ++j) v[j] = vh[j] * gelu_erf(vg[j]);
+  for (int j = 0; j < 4; ++j) v[j] = vh[j] * (ACT == VDA_ACT_SWIGLU ? silu_f32(vg[j]) : gelu_erf(vg[j]));
   const int nout_tot = p.N >> 1;
   if (e.gamma) v *= *reinterpret_cast<const f4*>(e.gamma + n_out);
   if (e.res) {
@@ -284,7 +285,7 @@ __global__ __launch_bounds__(256) void gemm_reg_kernel(GemmParams p, int tiles_n
 
   // epilogue: lane holds D[n = 4*(lane>>4) + r][m = lane&15] of every (i, j) subtile
   const int mcol = lane & 15, nq = (lane >> 4) * 4;
-  if constexpr (ACT == VDA_ACT_GEGLU) {
+  if constexpr (vda_glu(ACT)) {
 #pragma unroll
     for (int i = 0; i < TN; i += 2) {
       const int nbase = n0 + wn * (BN / 2) + i * 16;  // h block; gate block = nbase + 16
@@ -293,7 +294,7 @@ __global__ __launch_bounds__(256) void gemm_reg_kernel(GemmParams p, int tiles_n
 #pragma unroll
       for (int j = 0; j < TM; ++j) {
         int m = m0 + wm * (BM / 2) + j * 16 + mcol;
-        if (m < p.M) epi_geglu4(p, m, nbase + nq, nbase + 16 + nq, n_out, acc[i][j], acc[i + 1][j]);
+        if (m < p.M) epi_geglu4<ACT>(p, m, nbase + nq, nbase + 16 + nq, n_out, acc[i][j], acc[i + 1][j]);
       }
     }
   } else {
@@ -325,7 +326,7 @@ __device__ __attribute__((aligned(64))) uint4 g_zero_page[4];
 #define VDA_GROUP_M 8
 #endif
 constexpr int GROUP_M = VDA_GROUP_M;  // m-panels per XCD tile group (2 / 4 / 16 within noise: profiles/r04_ab_gemm_group_m.log)
-constexpr int ACT_DEPTH = 4;  // internal: depth-head tail epilogue (vda_depth_head)
+constexpr int ACT_DEPTH = 100;  // internal (outside the VDA_ACT_* codes): depth-head tail epilogue (vda_depth_head)
 
 __device__ __forceinline__ void tile_coords(int bid, int nwg, int tiles_m, int tiles_n, int& tm, int& tn) {
   const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
@@ -499,8 +500,8 @@ __global__ __launch_bounds__(NWM * NWN * 64) void gemm_kernel(GemmParams p, int 
       const int m = m0 + wm * WTM + j * 16 + mcol;
       if (lane < 16 && m < p.M) reinterpret_cast<float*>(p.y)[m] = fmaxf(part + b2, 0.f);
     }
-  } else if constexpr (ACT == VDA_ACT_GEGLU) {
-    static_assert(TN % 2 == 0, "GEGLU needs an even number of n subtiles per wave");
+  } else if constexpr (vda_glu(ACT)) {
+    static_assert(TN % 2 == 0, "GEGLU / SwiGLU needs an even number of n subtiles per wave");
 #pragma unroll
     for (int i = 0; i < TN; i += 2) {
       const int nbase = n0 + wn * WTN + i * 16;
@@ -509,7 +510,7 @@ __global__ __launch_bounds__(NWM * NWN * 64) void gemm_kernel(GemmParams p, int 
 #pragma unroll
       for (int j = 0; j < TM; ++j) {
         const int m = m0 + wm * WTM + j * 16 + mcol;
-        if (m < p.M) epi_geglu4(p, m, nbase + nq, nbase + 16 + nq, n_out, acc[i][j], acc[i + 1][j]);
+        if (m < p.M) epi_geglu4<ACT>(p, m, nbase + nq, nbase + 16 + nq, n_out, acc[i][j], acc[i + 1][j]);
       }
     }
   } else {

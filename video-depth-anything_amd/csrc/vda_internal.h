@@ -5,6 +5,8 @@
 #pragma once
 #include "vda_common.h"
 #include "../../include/vda.h"
+static_assert(vda_glu(VDA_ACT_GEGLU) && vda_glu(VDA_ACT_SWIGLU) && !vda_glu(VDA_ACT_GELU) && !vda_glu(VDA_ACT_RELU),
+              "vda_glu (vda_common.h) names the gated activation codes of vda.h");
 
 // ---- vda_gemm.hip: the MFMA GEMM / implicit-GEMM conv kernels behind plain launch functions ----
 struct GemmParams {

@@ -122,7 +122,7 @@ Tensor gemm_into(const Tensor& x, const Tensor& w, OptT bias, OptT rowbias, int6
   need_contig(w, dt, "w", x);
   TORCH_CHECK(w.dim() == 2 && w.size(1) == x.size(1), "vda gemm: K mismatch ", w.sizes(), " vs ", x.sizes());
   const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
-  const int64_t nout = act == VDA_ACT_GEGLU ? N / 2 : N;
+  const int64_t nout = (act == VDA_ACT_GEGLU || act == VDA_ACT_SWIGLU) ? N / 2 : N;
   TORCH_CHECK(drop_period >= 0, "vda gemm: drop_period >= 0");
   const int64_t Mo = gemm_out_rows(M, drop_period);
   TORCH_CHECK(out.dim() == 2 && out.size(0) == Mo && out.size(1) == nout && out.stride(1) == 1 &&
@@ -157,7 +157,7 @@ Tensor gemm(const Tensor& x, const Tensor& w, OptT bias, OptT rowbias, int64_t r
             OptT stats_out, OptT sched, int64_t drop_period) {
   const auto dt = act_dtype(x);
   TORCH_CHECK(x.dim() == 2 && w.dim() == 2, "vda gemm: x and w must be 2-D");
-  const int64_t nout = act == VDA_ACT_GEGLU ? w.size(0) / 2 : w.size(0);
+  const int64_t nout = (act == VDA_ACT_GEGLU || act == VDA_ACT_SWIGLU) ? w.size(0) / 2 : w.size(0);
   Tensor out = at::empty({gemm_out_rows(x.size(0), drop_period), nout}, x.options().dtype(dt));
   return gemm_into(x, w, bias, rowbias, rdiv, rmod, gamma, res, res2, act, ln_stats, ln_colsum, ln_parts, ln_eps,
                    stats_out, sched, drop_period, out);

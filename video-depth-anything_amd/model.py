@@ -23,19 +23,23 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from ._lib import ACT_GELU, ACT_GEGLU, ACT_RELU
+from ._lib import ACT_GELU, ACT_GEGLU, ACT_RELU, ACT_SWIGLU
 
 PATCH = 14
 ENCODER_CFG = {
     "vits": dict(embed_dim=384, depth=12, heads=6, taps=[2, 5, 8, 11]),
     "vitb": dict(embed_dim=768, depth=12, heads=12, taps=[2, 5, 8, 11]),
     "vitl": dict(embed_dim=1024, depth=24, heads=16, taps=[4, 11, 17, 23]),
+    # dinov2.py:381-415 vit_giant2 with ffn_layer="swiglufused"; the reference has no tap list for it: these are
+    # Depth-Anything-V2's.  ffn: "mlp" (fc1 / GELU / fc2, the default) or "swiglu" (w12 / w3)
+    "vitg": dict(embed_dim=1536, depth=40, heads=24, taps=[9, 19, 29, 39], ffn="swiglu"),
 }
 # run.py:74-77 model_configs
 MODEL_CONFIGS = {
     "vits": dict(encoder="vits", features=64, out_channels=[48, 96, 192, 384]),
     "vitb": dict(encoder="vitb", features=128, out_channels=[96, 192, 384, 768]),
     "vitl": dict(encoder="vitl", features=256, out_channels=[256, 512, 1024, 1024]),
+    "vitg": dict(encoder="vitg", features=384, out_channels=[1536, 1536, 1536, 1536]),
 }
 
 
@@ -63,14 +67,22 @@ class Mlp(nn.Module):  # mlp.py:17-33
         self.fc2 = nn.Linear(hidden, dim)
 
 
+class SwiGLUFFNFused(nn.Module):  # swiglu_ffn.py:14-63: w3(silu(x1) * x2), x1, x2 = w12(x).chunk(2)
+    def __init__(self, dim, hidden):
+        super().__init__()
+        hidden = (int(hidden * 2 / 3) + 7) // 8 * 8
+        self.w12 = nn.Linear(dim, 2 * hidden)
+        self.w3 = nn.Linear(hidden, dim)
+
+
 class Block(nn.Module):  # block.py:36-80
-    def __init__(self, dim, heads):
+    def __init__(self, dim, heads, ffn="mlp"):
         super().__init__()
         self.norm1 = nn.LayerNorm(dim, eps=1e-6)
         self.attn = Attention(dim, heads)
         self.ls1 = LayerScale(dim)
         self.norm2 = nn.LayerNorm(dim, eps=1e-6)
-        self.mlp = Mlp(dim, 4 * dim)
+        self.mlp = SwiGLUFFNFused(dim, 4 * dim) if ffn == "swiglu" else Mlp(dim, 4 * dim)
         self.ls2 = LayerScale(dim)
 
 
@@ -91,7 +103,7 @@ class DinoVisionTransformer(nn.Module):  # dinov2.py:44-170, DINOv2() factory :3
         self.patch_embed = PatchEmbed(C)
         self.cls_token = nn.Parameter(torch.zeros(1, 1, C))
         self.pos_embed = nn.Parameter(torch.zeros(1, (518 // PATCH) ** 2 + 1, C))
-        self.blocks = nn.ModuleList([Block(C, cfg["heads"]) for _ in range(cfg["depth"])])
+        self.blocks = nn.ModuleList([Block(C, cfg["heads"], cfg.get("ffn", "mlp")) for _ in range(cfg["depth"])])
         self.norm = nn.LayerNorm(C, eps=1e-6)
         self.mask_token = nn.Parameter(torch.zeros(1, C))
 
@@ -226,6 +238,39 @@ def _geglu_interleave(t):
     return torch.cat(blocks, 0)
 
 
+def _swiglu_interleave(t):
+    """SwiGLUFFNFused w12 rows [x1(0..I-1); x2(0..I-1)] (gate first, swiglu_ffn.py:34-36) -> the GEGLU block layout
+    with h = x2, g = x1 (vda.h VDA_ACT_SWIGLU: y = silu(g) * h)."""
+    inner = t.shape[0] // 2
+    return _geglu_interleave(torch.cat([t[inner:], t[:inner]], 0))
+
+
+def _ln_fold_terms(weight, bias, ln, wd):
+    """A LayerNorm folded into the Linear after it: (W' = gamma (.) W stored as ``wd``, colsum = sum_k W' of the stored
+    values, b' = W beta + b).  fp32 arithmetic (float64 for float64 parameters, which the packing test uses)."""
+    acc = torch.float64 if weight.dtype == torch.float64 else torch.float32
+    w = weight.detach().to(acc)
+    wg = (w * ln.weight.detach().to(acc)[None, :]).to(wd).contiguous()
+    c1 = wg.to(acc).sum(1).contiguous()
+    bb = (w @ ln.bias.detach().to(acc) + bias.detach().to(acc)).contiguous()
+    return wg, c1, bb
+
+
+def _pack_ffn_in(blk, wd, lnfold):
+    """The first FFN GEMM of an encoder block, fc1 or (SwiGLU) w12 -> (w, colsum or None, bias), not yet moved to the kernels' device: norm2
+    folded in when ``lnfold`` (block.py:87), and for SwiGLU the rows [x1; x2] = [gate; value] then interleaved into
+    the kernel's 16-row [h | g] = [x2 | x1] blocks (vda.h VDA_ACT_SWIGLU), weight, colsum and bias alike."""
+    swiglu = isinstance(blk.mlp, SwiGLUFFNFused)
+    l1 = blk.mlp.w12 if swiglu else blk.mlp.fc1
+    if lnfold:
+        w, c1, b = _ln_fold_terms(l1.weight, l1.bias, blk.norm2, wd)
+    else:
+        w, c1, b = l1.weight.detach().to(wd).contiguous(), None, _f(l1.bias)
+    if swiglu:
+        w, c1, b = (t if t is None else _swiglu_interleave(t).contiguous() for t in (w, c1, b))
+    return w, c1, b
+
+
 class _Packed:
     pass
 
@@ -320,11 +365,7 @@ class VideoDepthAnything(nn.Module):
         P.lnfold = not fp32 and bool(self.fold_layernorms)
 
         def _ln_fold(weight, bias, ln):
-            w = weight.detach().float()
-            wg = (w * ln.weight.detach().float()[None, :]).to(wd).contiguous()
-            c1 = wg.float().sum(1).contiguous()
-            bb = (w @ ln.bias.detach().float() + bias.detach().float()).contiguous()
-            return wg.to(dev), c1.to(dev), bb.to(dev)
+            return tuple(t.to(dev) for t in _ln_fold_terms(weight, bias, ln, wd))
 
         for b in enc.blocks:
             q = _Packed()
@@ -339,13 +380,13 @@ class VideoDepthAnything(nn.Module):
             q.proj_w = _h(b.attn.proj.weight.detach().float() * g1[:, None]).to(dev)
             q.proj_b = _f(b.attn.proj.bias.detach().float() * g1).to(dev)
             q.n2w, q.n2b = _f(b.norm2.weight).to(dev), _f(b.norm2.bias).to(dev)
-            if P.lnfold:
-                q.fc1_w, q.fc1_c1, q.fc1_b = _ln_fold(b.mlp.fc1.weight, b.mlp.fc1.bias, b.norm2)
-            else:
-                q.fc1_w, q.fc1_b = _h(b.mlp.fc1.weight).to(dev), _f(b.mlp.fc1.bias).to(dev)
+            # SwiGLU blocks (ViT-g): w12 / w3 take fc1 / fc2's places (_pack_ffn_in)
+            q.swiglu = isinstance(b.mlp, SwiGLUFFNFused)
+            l2 = b.mlp.w3 if q.swiglu else b.mlp.fc2
+            q.fc1_w, q.fc1_c1, q.fc1_b = (t if t is None else t.to(dev) for t in _pack_ffn_in(b, wd, P.lnfold))
             g2 = b.ls2.gamma.detach().float()
-            q.fc2_w = _h(b.mlp.fc2.weight.detach().float() * g2[:, None]).to(dev)
-            q.fc2_b = _f(b.mlp.fc2.bias.detach().float() * g2).to(dev)
+            q.fc2_w = _h(l2.weight.detach().float() * g2[:, None]).to(dev)
+            q.fc2_b = _f(l2.bias.detach().float() * g2).to(dev)
             P.blocks.append(q)
         P.nw, P.nb = _f(enc.norm.weight).to(dev), _f(enc.norm.bias).to(dev)
 
@@ -609,15 +650,16 @@ class VideoDepthAnything(nn.Module):
             at = ops.spatial_attention(qkv, BT, ntok, P.heads, 64)
             del qkv
             ops.gemm(at, q.proj_w, bias=q.proj_b, res=tok, out=tok, stats_out=st_a if epistats else None, sched=sch)
-            if P.lnfold:  # norm2 folded into the fc1 GEMM
+            act1 = ACT_SWIGLU if q.swiglu else ACT_GELU  # mlp.py:36-39 fc1 + GELU | swiglu_ffn.py w12 + silu gate
+            if P.lnfold:  # norm2 folded into the fc1 (w12) GEMM
                 if epistats:
                     stats, parts = st_a, nparts
                 else:
                     stats, parts = ops.row_stats(tok, 1e-6), 0
-                f = ops.gemm(tok, q.fc1_w, bias=q.fc1_b, act=ACT_GELU, ln_stats=stats, ln_parts=parts, ln_eps=1e-6,
+                f = ops.gemm(tok, q.fc1_w, bias=q.fc1_b, act=act1, ln_stats=stats, ln_parts=parts, ln_eps=1e-6,
                              ln_colsum=q.fc1_c1, sched=sch, tag="enc_fc1")
             else:
-                f = ops.gemm(ops.layernorm(tok, q.n2w, q.n2b, 1e-6), q.fc1_w, bias=q.fc1_b, act=ACT_GELU,
+                f = ops.gemm(ops.layernorm(tok, q.n2w, q.n2b, 1e-6), q.fc1_w, bias=q.fc1_b, act=act1,
                              tag="enc_fc1")
             last = i + 1 == len(P.blocks)
             ops.gemm(f, q.fc2_w, bias=q.fc2_b, res=tok, out=tok,

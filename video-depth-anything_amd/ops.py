@@ -15,7 +15,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import ACT_NONE, ACT_GELU, ACT_GEGLU, ACT_RELU, STORE_ROWS, STORE_PIXEL_SHUFFLE  # noqa: F401
+from ._lib import ACT_NONE, ACT_GELU, ACT_GEGLU, ACT_RELU, ACT_SWIGLU, STORE_ROWS, STORE_PIXEL_SHUFFLE  # noqa: F401
 
 Tensor = torch.Tensor
 
@@ -58,7 +58,7 @@ def _need(t: Tensor, dtype, name: str):
 def gemm(x: Tensor, w: Tensor, *, bias=None, rowbias=None, rdiv=1, rmod=1, gamma=None, res=None,
          res2=None, act=ACT_NONE, ln_stats=None, ln_colsum=None, ln_parts=0, ln_eps=1e-6, stats_out=None,
          sched=None, drop_period=0, out: Optional[Tensor] = None, tag: Optional[str] = None) -> Tensor:
-    """out[M, N'] = epi(x[M, K] @ w[N, K]^T); N' = N (N/2 for GEGLU). x may be a row-strided view.
+    """out[M, N'] = epi(x[M, K] @ w[N, K]^T); N' = N (N/2 for GEGLU / SwiGLU). x may be a row-strided view.
     fp16 x/w -> vda_gemm; fp32 x/w -> vda_gemm_f32 (fp32 mode).  torch.ops.vda.gemm[.out].
     ``ln_stats`` + ``ln_colsum`` fold a LayerNorm of x into the GEMM (vda.h): ln_stats is either
     ``row_stats(x)`` ([M, 2] (mean, rstd), ln_parts=0) or the [M, P, 2] partial sums another GEMM wrote
@@ -96,7 +96,7 @@ def gemm_accepts(M: int, N: int, K: int, *, bias=True, ln_fold=False, ln_parts=0
     LN fold + ``rowbias``) and separate ops.  Memoised per argument tuple: a steady-state forward asks the
     library nothing."""
     ptr = lambda on: 0x1000 if on else None  # noqa: E731  (only null-ness and alignment are looked at)
-    ny = N // 2 if act == ACT_GEGLU else N
+    ny = N // 2 if act in (ACT_GEGLU, ACT_SWIGLU) else N
     e = _lib.Epilogue(bias=ptr(bias), rowbias=ptr(rowbias), rdiv=int(rdiv), rmod=int(rmod), res=ptr(res), ldres=ny,
                       act=int(act), ln_stats=ptr(ln_fold), ln_colsum=ptr(ln_fold), ln_parts=int(ln_parts),
                       stats_out=ptr(stats_out), drop_period=int(drop_period))
