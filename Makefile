@@ -21,9 +21,12 @@ all: $(PKG)/libvda.so $(PKG)/libvda_torch.so
 build/vda_attn.o: EXTRA := -fno-honor-nans -fno-slp-vectorize
 # GEMM epilogues: SLP packing of scalar f32 math needs register moves that cost more than it saves
 build/vda_gemm.o: EXTRA := -fno-slp-vectorize
+# source-resolution output_conv1: its blend is scalar f32 FMAs beside MFMAs (packed f32 VALU loses there)
+build/vda_oc1_src.o: EXTRA := -fno-slp-vectorize
 
 build/tune/vda_attn.o: EXTRA := -fno-honor-nans -fno-slp-vectorize
 build/tune/vda_gemm.o: EXTRA := -fno-slp-vectorize
+build/tune/vda_oc1_src.o: EXTRA := -fno-slp-vectorize
 DEPS := $(addprefix $(PKG)/csrc/,vda_common.h vda_stream.h vda_lut.h vda_halo.h vda_internal.h vda_tune.h vda_gemm_tile.h vda_gemm_phased.h vda_preprocess.h phi_table.h) include/vda.h include/vda_tune.h
 
 build/%.o: $(PKG)/csrc/%.hip $(DEPS)

@@ -31,6 +31,12 @@ int vda_debug_hconv(int32_t mode);
  * a materialised resize (bit-identical; needs the workspace).  Any other value is refused (non-zero return,
  * knob unchanged). */
 int vda_debug_dconv(int32_t mode);
+/* 3x3 conv with 128 outputs through an exact x2 resize (output_conv1): 1 = automatic (the kernel that mixes the
+ * channels at the source resolution, vda_oc1_src.hip, for a call with a bias9 table; a plain-bias call keeps the
+ * halo conv with the fused resize and with it the bits of resize + conv), 2 = the source-resolution kernel
+ * wherever it serves, 0 = the halo conv with the fused resize for every shape.  Any other value is refused
+ * (non-zero return, knob unchanged). */
+int vda_debug_oc1_src(int32_t mode);
 /* Temporal attention: 1 = the direct-load kernel for every head dim (0 = automatic: the LDS-staged one
  * where it applies). */
 int vda_debug_attn(int32_t temporal_direct);

@@ -2,6 +2,7 @@
 
 usage: python tools/ab_conv.py LIB_A.so[@knob=v] [LIB_B.so ...] [--rounds R] [--shapes oc1,depth,rcu148]
 oc1:    output_conv1, 3x3 256 -> 128 on the x2 bilinear resize of a [32, 148, 148, 256] map (fused)
+oc1w:   the same on a [32, 148, 264, 256] map (the 518 x 924 clip)
 oc1u:   the same through the materialised resize + the plain halo conv (compare with oc1: same output)
 depth:  the depth tail on the [32, 296, 296, 128] output_conv1 map, resized to 518 x 518 (fused)
 rcu148: refinenet1 RCU conv, 3x3 256 -> 256 at 148^2 with pre-ReLU + ReLU
@@ -44,16 +45,17 @@ st = torch.cuda.current_stream().cuda_stream
 
 
 def case(name):
-    if name == "oc1":
-        x = (torch.randn(32, 148, 148, 256, device=dev) * 0.5).half()
+    if name in ("oc1", "oc1w"):
+        ws = 148 if name == "oc1" else 264
+        x = (torch.randn(32, 148, ws, 256, device=dev) * 0.5).half()
         w = (torch.randn(128, 3, 3, 256, device=dev) * (9 * 256) ** -0.5).half()
         b = torch.randn(128, device=dev) * 0.1
-        y = torch.empty(32, 296, 296, 128, device=dev, dtype=torch.float16)
+        y = torch.empty(32, 296, 2 * ws, 128, device=dev, dtype=torch.float16)
         e = _lib.Epilogue(rdiv=1, rmod=1, bias=b.data_ptr())
-        fl = 2.0 * 32 * 296 * 296 * 128 * 2304
+        fl = 2.0 * 32 * 296 * 2 * ws * 128 * 2304  # the FLOPs of the conv at the output resolution
 
         def run(l):
-            return l.vda_conv2d(x.data_ptr(), w.data_ptr(), y.data_ptr(), 32, 148, 148, 256, 128, 3, 1, 1, 0, 296, 296,
+            return l.vda_conv2d(x.data_ptr(), w.data_ptr(), y.data_ptr(), 32, 148, ws, 256, 128, 3, 1, 1, 0, 296, 2 * ws,
                                 ctypes.byref(e), None, 0, st)
         return run, y, fl, [x, w, b, e]
     if name == "oc1u":  # the unfused route: the x2 resize materialised, then the plain halo conv at 296^2

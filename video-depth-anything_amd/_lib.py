@@ -41,7 +41,7 @@ EXPORTED = (
 )
 # The tuning build (make tune -> build/tune/libvda.so, include/vda_tune.h) adds these.
 TUNE_EXPORTED = ("vda_debug_force_tile", "vda_debug_gemm_sched", "vda_debug_strip_split", "vda_debug_hconv",
-                 "vda_debug_dconv", "vda_debug_attn")
+                 "vda_debug_dconv", "vda_debug_attn", "vda_debug_oc1_src")
 TUNE_LIB_PATH = os.path.join(os.path.dirname(_HERE), "build", "tune", "libvda.so")
 
 ACT_NONE, ACT_GELU, ACT_GEGLU, ACT_RELU, ACT_SWIGLU = 0, 1, 2, 3, 4
@@ -153,6 +153,7 @@ def _declare(lib):
         "vda_debug_hconv": ([I], I),
         "vda_debug_dconv": ([I], I),
         "vda_debug_attn": ([I], I),
+        "vda_debug_oc1_src": ([I], I),
     }
     for name, (args, res) in sig.items():
         if name.startswith("vda_debug_") and not hasattr(lib, name):

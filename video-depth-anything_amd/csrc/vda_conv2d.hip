@@ -105,6 +105,11 @@ extern "C" int vda_conv2d(const void* x, const void* w, void* y, int32_t BT, int
     // halo conv with the resize fused into its patch staging (bit-identical to resize + conv)
     if (g_force_tile < 0 && ks == 3 && stride == 1 && pad == 1 && !pre_relu && !p.epi.res && !p.epi.res2 &&
         !p.epi.gamma && !p.epi.rowbias) {
+      // an exact x2 resize with a bias9 table: the channel mixing at the source resolution, a quarter of the
+      // matrix work (vda_oc1_src.hip; same linear map, not the same bits, so a plain-bias call is not routed there)
+      rc = vda_conv_oc1_src(x, w, y, p.epi.bias, p.epi.act == VDA_ACT_RELU, BT, H, W, p.up_h, p.up_w, Cin, Cout,
+                            (hipStream_t)stream, p.epi.bias9);
+      if (rc != 1) return rc;
       rc = vda_conv_halo_fused(x, w, y, p.epi.bias, p.epi.act == VDA_ACT_RELU, BT, H, W, p.up_h, p.up_w, Cin, Cout,
                                (hipStream_t)stream, p.epi.bias9);
       if (rc != 1) return rc;

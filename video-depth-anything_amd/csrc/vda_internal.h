@@ -51,6 +51,13 @@ int vda_conv_halo_fused(const void* x, const void* w, void* y, const float* bias
                         int H, int W, int Cin, int Cout, hipStream_t st, const float* bias9 = nullptr);
 bool vda_conv_halo_fused_serves(int BT, int Hs, int Ws, int H, int W, int Cin, int Cout);
 
+// ---- vda_oc1_src.hip: the same conv through an exact x2 resize, channel mixing at the source resolution ----
+// arguments and semantics of vda_conv_halo_fused; serves (H, W) = (2 Hs, 2 Ws), Cin % 64 == 0 (<= 256), Cout = 128,
+// in the product for a bias9 call only (a plain-bias call keeps the bits of resize + conv)
+bool vda_conv_oc1_src_serves(int BT, int Hs, int Ws, int H, int W, int Cin, int Cout, bool bias9);
+int vda_conv_oc1_src(const void* x, const void* w, void* y, const float* bias, int relu, int BT, int Hs, int Ws, int H,
+                     int W, int Cin, int Cout, hipStream_t st, const float* bias9 = nullptr);
+
 // ---- vda_dconv.hip: depth-tail conv on the resized map, 2 blocks / CU ----
 bool vda_depth_conv_serves(int H, int W, int C);
 int vda_depth_conv(const void* U, const void* w1, const float* b1, const float* w2, const float* b2, float* depth,

@@ -793,7 +793,8 @@ class VideoDepthAnything(nn.Module):
         # (fp16: the halo conv builds each patch by interpolation; fp32 mode materialises the resize)
         if P.fp32:
             o1 = ops.conv2d(ops.upsample_bilinear(y, H1, W1), P.oc1_w, bias=P.oc1_b)
-        elif fold_out:  # W_oc1[t] W_out on the map before out_conv, the bias by class of the output pixel
+        elif fold_out:  # W_oc1[t] W_out on the map before out_conv, the bias by class of the output pixel; with a
+            # bias9 table the x2 case runs its channel mixing at the source resolution (csrc/vda_oc1_src.hip)
             wc, b9 = self._pack_oc1(P)
             o1 = ops.conv2d(y, wc, bias9=b9, up=(H1, W1))
         else:
