@@ -12,6 +12,13 @@
  *   half   = IEEE fp16 (_Float16), float = fp32.
  *   Activations are token-major / NHWC: a [BT, h, w, C] feature map is a [BT*h*w, C] matrix.
  *   Linear / conv weights are fp16, K (input channel) contiguous; biases are fp32.
+ *   Alignment: where an entry point states nothing else, every device pointer is 16-byte aligned at its base
+ *   (matrices, maps, weights, qkv, workspaces, and the fp32 per-channel / per-row operands bias, rowbias, gamma,
+ *   beta, ln_colsum, ln_stats, stats_out, bias9), and no kernel reads or writes outside the elements the shapes
+ *   and row strides name: what lies before an operand, after it and between the rows of a strided view is never
+ *   loaded into a result (tests/test_gpu_placement.py places every operand at exactly its stated alignment
+ *   between NaN / Inf zones).  vda_gemm also takes y, res and res2 at the 8-byte alignment their N % 4 == 0 row
+ *   strides imply (the one-tile kernels then serve the call).
  *
  * The reference (FriedFeid/Video-Depth-Anything @ /root/reference) has no native layer or FFI:
  * its hot path is PyTorch modules.  Each entry point below names the reference code it replaces.

@@ -28,12 +28,31 @@ def _rows(x):  # [BT, C, h, w] -> [BT*h*w, C] fp16 on the GPU
     return SL.map_to_rows(x)
 
 
+SENT, GUARD = -7776.0, 1024  # the sentinel (exact in fp16) and its count before and after the output
+
+
 def _fused(c: Case, wq=None, b9=None, x=None):
+    """vda_subpixel_conv through the C ABI into an output between sentinel guards that must be intact afterwards,
+    its workspace of exactly vda_subpixel_conv_workspace() bytes inside a guard of its own; ops.subpixel_conv (the
+    product's call, which allocates both) must return the same bits."""
     if wq is None:
         wq, b9 = weights.compose_subpixel(c.wt, c.bt, c.wr, c.s)
     x = c.x if x is None else x
-    y = ops.subpixel_conv(_rows(x), wq.cuda(), b9.cuda(), c.BT, c.h, c.w, c.s)
-    assert y.shape == (c.BT, c.s * c.h, c.s * c.w, CHAINS[c.s][2])
+    L = vda_amd._libvda()
+    Cin, _, Cout = CHAINS[c.s]
+    xr, wd, bd = _rows(x), wq.cuda(), b9.cuda()
+    n = c.BT * c.s * c.h * c.s * c.w * Cout
+    buf = torch.full((n + 2 * GUARD,), SENT, dtype=torch.float16, device="cuda")
+    y = buf[GUARD:GUARD + n].view(c.BT, c.s * c.h, c.s * c.w, Cout)
+    wsb = int(L.vda_subpixel_conv_workspace(c.BT, c.h, c.w, Cin, c.s))
+    wbuf = torch.full((wsb + 2 * GUARD,), 0x5A, dtype=torch.uint8, device="cuda")
+    rc = L.vda_subpixel_conv(xr.data_ptr(), wd.data_ptr(), bd.data_ptr(), y.data_ptr(), c.BT, c.h, c.w, Cin, Cout, c.s,
+                             wbuf[GUARD:].data_ptr(), wsb, torch.cuda.current_stream().cuda_stream)
+    assert rc == 0, L.vda_last_error().decode()
+    torch.cuda.synchronize()
+    assert bool((buf[:GUARD] == SENT).all()) and bool((buf[-GUARD:] == SENT).all()), "a store outside the output"
+    assert bool((wbuf[:GUARD] == 0x5A).all()) and bool((wbuf[-GUARD:] == 0x5A).all()), "a store outside the workspace"
+    assert torch.equal(y, ops.subpixel_conv(xr, wd, bd, c.BT, c.h, c.w, c.s))
     return y
 
 

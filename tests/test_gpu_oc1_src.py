@@ -32,14 +32,19 @@ pytestmark = pytest.mark.gpu
 SHAPES = MAPS3 + [(1, 17, 9), (2, 1, 2), (1, 24, 8)]
 
 
+SENT, GUARD = -7776.0, 1024  # the sentinel (exact in fp16) and its count before and after every output
+
+
 def conv_up(route: int, x, w, up, bias=None, bias9=None):
     """vda_conv2d (3x3 / s1 / p1) of NHWC fp16 x through the resize to `up` (None: no resize), tuning library with
-    vda_debug_oc1_src(route)."""
+    vda_debug_oc1_src(route), into an output between sentinel guards that must be intact afterwards."""
     T = tune_lib()
     BT, H, W, Cin = x.shape
     Cout = w.shape[0]
     Ho, Wo = (H, W) if up is None else up
-    y = torch.empty(BT, Ho, Wo, Cout, dtype=torch.float16, device=x.device)
+    n = BT * Ho * Wo * Cout
+    buf = torch.full((n + 2 * GUARD,), SENT, dtype=torch.float16, device=x.device)
+    y = buf[GUARD:GUARD + n].view(BT, Ho, Wo, Cout)
     e = _lib.Epilogue(rdiv=1, rmod=1)
     if bias is not None:
         e.bias = bias.data_ptr()
@@ -54,6 +59,7 @@ def conv_up(route: int, x, w, up, bias=None, bias9=None):
         assert T.lib.vda_debug_oc1_src(1) == 0
     assert rc == 0, T.lib.vda_last_error().decode()
     torch.cuda.synchronize()
+    assert bool((buf[:GUARD] == SENT).all()) and bool((buf[-GUARD:] == SENT).all()), "a store outside the output"
     return y
 
 

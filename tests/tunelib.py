@@ -115,7 +115,8 @@ class TuneLib:
         return y
 
     def gemm_kw(self, x, w, out, *, bias=None, rowbias=None, rdiv=1, rmod=1, gamma=None, res=None, res2=None, act=0,
-                ps=None, ln_stats=None, ln_colsum=None, ln_parts=0, ln_eps=1e-6, stats_out=None, drop_period=0):
+                ps=None, ln_stats=None, ln_colsum=None, ln_parts=0, ln_eps=1e-6, stats_out=None, drop_period=0,
+                sched=None):
         """vda_gemm with the epilogue given by keyword (the ops.gemm names) into `out`, any row-strided 2-D fp16
         view (or, with ps=(k, cout, hin, win), the contiguous pixel-shuffled NHWC output).  x [M, K] and res /
         res2 may be row-strided views; the tensors must stay alive until the stream has run the launch."""
@@ -123,7 +124,7 @@ class TuneLib:
         N = w.shape[0]
         e = _lib.Epilogue(rdiv=rdiv, rmod=rmod, act=act, ln_parts=ln_parts, ln_eps=ln_eps, drop_period=drop_period)
         for name, t in (("bias", bias), ("rowbias", rowbias), ("gamma", gamma), ("ln_stats", ln_stats),
-                        ("ln_colsum", ln_colsum), ("stats_out", stats_out)):
+                        ("ln_colsum", ln_colsum), ("stats_out", stats_out), ("sched", sched)):
             if t is not None:
                 setattr(e, name, t.data_ptr())
         if res is not None:
