@@ -209,14 +209,16 @@ def emulate_gemm(x, w, *, bias=None, rowbias=None, rdiv=1, rmod=1, gamma=None, r
     return v.half()
 
 
-def row_stats_ref_bound(y16):
+def row_stats_ref_bound(y16, part=256):
     """The stats_out partials of stored fp16 rows y16 [M, parts * 256]: (sum, sum of squares) per 256-column part
     in float64 [M, parts, 2] and their bound: a 256-term fp32 sum in any order (per lane, across lanes, across
-    the four waves of a block) with the squares' own roundings, gamma(256 + 8) of the absolute sums."""
-    y = d(y16).reshape(y16.shape[0], -1, 256)
+    the four waves of a block) with the squares' own roundings, gamma(256 + 8) of the absolute sums.
+    part: the width of a part where the row is narrower than 256 columns (N = 128: one part of 128 terms,
+    gamma(128 + 8))."""
+    y = d(y16).reshape(y16.shape[0], -1, part)
     ref = torch.stack([y.sum(-1), (y * y).sum(-1)], -1)
     A = torch.stack([y.abs().sum(-1), (y * y).sum(-1)], -1)
-    return ref, gam(256 + 8) * A + 2.0 ** -100
+    return ref, gam(part + 8) * A + 2.0 ** -100
 
 
 def emulate_row_stats(y16):
@@ -524,6 +526,18 @@ def conv_case(BT, Cin, Cout, H, W, mode, *, ks=3, stride=1, seed=0, res2_src=Non
     elif mode != "plain":
         raise ValueError(mode)
     return c
+
+
+# ViT-B's 3x3 convs with 128 outputs (layer1..4_rn, the refinenets' RCU convs) on the phased 512x128 kernel:
+# (BT, H, W) with M = 8,281 = 16 x 512 + 89 (a ragged last tile) and M = 8,192 (whole tiles, the frame change on a
+# tile edge); Cin = 96 (K = 864: per-lane tap decode, a K tail of 32), 128 (wave-uniform taps), 8 (K = 72: two K
+# tiles, both straddling taps).  Shared by tests/test_gpu_vitb.py and the negative control of tests/test_vitb.py.
+VITB_CONV_SIZES = [(1, 91, 91), (2, 64, 64)]
+VITB_CONV_CINS = [96, 128, 8]
+
+
+def vitb_conv_case(BT, Cin, H, W, mode):
+    return conv_case(BT, Cin, 128, H, W, mode, seed=Cin + H)
 
 
 def attn_ramp_qkv(ramp, B, N, H, D=64, seed=7):
@@ -975,9 +989,9 @@ def gn_affine(C, seed=0):
     return rnd32(C, scale=0.1, seed=seed + 11) + 1, rnd32(C, scale=0.1, seed=seed + 12)
 
 
-# (C, groups): cg = 2, 4, 6, 8, 12, 32, 64; C = 24 / 48: 3 / 6 chunks per row leave idle threads in gn_layout;
+# (C, groups): cg = 2, 4, 6, 8, 12, 32, 64, and ViT-B's 12 / 24 of 32 groups (C = 384 / 768); C = 24 / 48: 3 / 6 chunks per row leave idle threads in gn_layout;
 # C = 2048: one row-lane (rpi = 1).  S around both gn_rows values (128 below C = 512, 32 from there).
-GN_SHAPES = [(64, 32), (128, 32), (24, 4), (256, 32), (48, 4), (1024, 32), (2048, 32)]
+GN_SHAPES = [(64, 32), (128, 32), (24, 4), (256, 32), (48, 4), (1024, 32), (2048, 32), (384, 32), (768, 32)]
 GN_S = [1, 2, 31, 32, 33, 127, 128, 129, 257]
 GN_FRAMES = [1, 3]
 

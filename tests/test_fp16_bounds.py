@@ -42,6 +42,21 @@ def test_gemm_emulation_within_bound(epi, staged):
     assert worst > 0.05  # the bound is within a small factor of what fp16 arithmetic really does
 
 
+@pytest.mark.parametrize("epi", ["gelu", "gamma_res", "res_res2"])
+def test_gemm_phased_512x128_emulation_within_bound(epi):
+    """The phased 512x128 kernel (XR = 4, ViT-B's N = 128 GEMMs) runs the staged epilogue (t rounded to fp16, then
+    packed fp16 residual adds) but has no Phi table (TAB is XR == 2 only): its GELU is gelu_erf.  That pair of
+    forms, staged=True with phi_table=False, at N = 128."""
+    worst = 0.0
+    for M, K in [(1, 8), (129, 40), (257, 512)]:
+        c = fb.gemm_case(M, 128, K, epi, seed=M)
+        ref, bound = fb.gemm_ref_bound(c["x"], c["w"], staged=True, phi_table=False, **c["kw"])
+        worst = max(worst, assert_elementwise(fb.emulate_gemm(c["x"], c["w"], staged=True, phi_table=False, **c["kw"]),
+                                              ref, bound, f"gemm 512x128 {epi} {M}x128x{K}"))
+    print(f"gemm 512x128 staged {epi}: worst emulation |y - ref| / bound = {worst:.3f}")
+    assert worst > 0.05
+
+
 @pytest.mark.parametrize("kind", fb.LN_KINDS)
 def test_gemm_ln_fold_emulation_within_bound(kind):
     c = fb.gemm_ln_case(257, 256, 192, kind, seed=3)
@@ -65,6 +80,11 @@ def test_row_stats_emulation_within_bound():
     ref, bound = fb.row_stats_ref_bound(y)
     worst = assert_elementwise(fb.emulate_row_stats(y), ref, bound, "stats_out partials")
     print(f"stats_out partials: worst emulation ratio {worst:.3f}")
+    y = (fb.rnd16(257, 128, seed=5) * 3 + 0.5).half()  # a row narrower than a part (N = 128): one 128-term part
+    ref, bound = fb.row_stats_ref_bound(y, part=128)
+    assert ref.shape == (257, 1, 2)
+    emu = y.float()
+    assert_elementwise(torch.stack([emu.sum(-1), (emu * emu).sum(-1)], -1)[:, None], ref, bound, "stats_out partials N=128")
 
 
 CONV_CASES = [
@@ -77,6 +97,9 @@ CONV_CASES = [
     ("implicit gemm s2", dict(BT=2, Cin=64, Cout=128, H=9, W=11, mode="rcu1", stride=2), False),
     ("implicit gemm 1x1", dict(BT=2, Cin=64, Cout=128, H=2, W=3, mode="rcu2", ks=1), False),
     ("phased conv rcu2", dict(BT=1, Cin=64, Cout=256, H=12, W=13, mode="rcu2"), True),
+    ("phased conv 512x128 Cin 96 rcu2", dict(BT=2, Cin=96, Cout=128, H=12, W=13, mode="rcu2"), True),
+    ("phased conv 512x128 Cin 8 rcu1", dict(BT=2, Cin=8, Cout=128, H=12, W=13, mode="rcu1"), True),
+    ("phased conv 256x256 Cin 96 rcu2", dict(BT=1, Cin=96, Cout=256, H=12, W=13, mode="rcu2"), True),
     ("resize + conv", dict(BT=2, Cin=64, Cout=128, H=8, W=20, mode="rcu1", up=(33, 47)), False),
 ]
 
@@ -119,7 +142,7 @@ def test_spatial_attention_ramps_emulation_within_bound(ramp):
 
 
 @pytest.mark.parametrize("rope", [0.0, 10000.0])
-@pytest.mark.parametrize("T,D", [(1, 32), (2, 8), (31, 64), (32, 128), (32, 24)])
+@pytest.mark.parametrize("T,D", [(1, 32), (2, 8), (31, 64), (32, 128), (32, 24), (2, 16), (32, 16), (31, 96), (32, 96), (32, 48)])
 def test_temporal_attention_emulation_within_bound(T, D, rope):
     B, S, H = 1, 3, 3
     qkv = fb.rnd16(B * T * S, 3 * H * D, seed=T + D) * 2

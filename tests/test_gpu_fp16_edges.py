@@ -474,10 +474,11 @@ def test_halo_fused_resize_edges(Hs, Ws, H, W):
     note(f"halo fused resize {Hs}x{Ws}->{H}x{W}", worst)
 
 
-@pytest.mark.parametrize("cfg", [-2, 0, 2, 3])
+@pytest.mark.parametrize("cfg", [-2, 0, 1, 2, 3])
 @pytest.mark.parametrize("H,W", [(1, 1), (2, 3), (9, 11), (16, 16)])
 def test_implicit_gemm_conv_edges(H, W, cfg):
-    """The implicit-GEMM conv (gemm_kernel<CONV>) by force_tile = -2 (automatic tile) and cfg 0 / 2 / 3: stride 1
+    """The implicit-GEMM conv (gemm_kernel<CONV>) by force_tile = -2 (automatic tile) and cfg 0 / 1 / 2 / 3 (1: the
+    256x128 tile the automatic route gives N = 128 convs of 4096 <= M < 8192 rows, ViT-B streaming): stride 1
     and 2, ks 1 and 3, Cin = 8 (the smallest: K = 8 or 72, a K tail) and 64, Cout = 32 and 128, BT = 2,
     plain / rcu1 / rcu2.  One rounding at the store."""
     worst = 0.0
@@ -491,7 +492,7 @@ def test_implicit_gemm_conv_edges(H, W, cfg):
     note(f"implicit-GEMM conv cfg {cfg} {H}x{W}", worst)
 
 
-@pytest.mark.parametrize("cfg", [-2, 0, 2])
+@pytest.mark.parametrize("cfg", [-2, 0, 1, 2])
 def test_implicit_gemm_conv_rowbias(cfg):
     """rowbias with rdiv = Ho * Wo (one bias row per frame, rmod = 3 over BT = 5 frames) on the implicit-GEMM
     conv at 9 x 11, stride 1 and 2: 128-row tiles span frame changes at rows that are no multiple of 16."""
@@ -544,6 +545,7 @@ ISOLATION = [
     ("implicit gemm s2", dict(force_tile=2), dict(Cin=64, Cout=128, H=9, W=11, mode="rcu1", stride=2), {}),
     ("im2col", {}, dict(Cin=64, Cout=256, H=127, W=131, mode="rcu1", stride=2), {}),
     ("phased conv", dict(hconv=0, force_tile=-2), dict(Cin=64, Cout=256, H=64, W=65, mode="rcu2"), {}),
+    ("phased conv 512x128", {}, dict(Cin=96, Cout=128, H=91, W=91, mode="rcu2"), {}),
 ]
 
 
@@ -644,7 +646,8 @@ def test_spatial_attention_ramps_elementwise(ramp, old):
 
 TEMPORAL = [(32, 4, 0), (64, 4, 0), (128, 4, 0),                 # the LDS-staged kernel (H % waves-per-block == 0)
             (8, 3, 0), (24, 3, 0), (48, 3, 0), (120, 3, 0),      # the direct-load kernel's own head dims
-            (64, 3, 0), (64, 4, 1), (32, 3, 1)]                  # direct-load: by H % 4 != 0 and by the attn knob
+            (64, 3, 0), (64, 4, 1), (32, 3, 1),                  # direct-load: by H % 4 != 0 and by the attn knob
+            (16, 8, 0), (96, 8, 0), (48, 8, 0)]                  # direct-load at H = 8: ViT-B's motion modules 2 / 3, 1, 0
 
 
 @pytest.mark.parametrize("rope", [0.0, 10000.0])
@@ -655,7 +658,9 @@ def test_temporal_attention_edges(D, H, old, rope):
     sentinel guards (no store for frames >= T or past the last site).  The LDS-staged kernel
     (D in {32, 64, 128}) only runs when H is a multiple of its waves per block, so it never has an idle wave:
     it gets H = 4 (S * H = 12 items); the direct-load kernel gets H = 3 (S * H = 9: one idle wave in the
-    last block of 4) at D in {8, 24, 48, 120}, at D = 64 (where H = 3 itself routes to it) and by the attn knob."""
+    last block of 4) at D in {8, 24, 48, 120}, at D = 64 (where H = 3 itself routes to it) and by the attn knob;
+    and at H = 8 (the motion modules' head count: S * H = 24 items, no idle wave) with D = 16, 96 and 48, ViT-B's
+    modules 2 / 3, 1 and 0, which no other encoder's head dims reach."""
     T = tune_lib()
     S, C = 3, H * D
     worst = 0.0
@@ -680,11 +685,12 @@ def test_temporal_attention_edges(D, H, old, rope):
 
 
 @pytest.mark.parametrize("rope", [0.0, 10000.0])
-@pytest.mark.parametrize("D,H", [(32, 4), (128, 2), (24, 3)])
+@pytest.mark.parametrize("D,H", [(32, 4), (128, 2), (24, 3), (16, 8), (96, 8)])
 def test_temporal_attention_batch_decode(D, H, rope):
     """The (item -> batch, site, head) decode both temporal kernels share, at B = 2 (the edges test has B = 1
     only), T = 5, S = 2: both block shapes of the LDS-staged kernel (4 waves at D = 32, 2 at D = 128) and the
-    direct-load kernel (D = 24, H = 3: 6 items in the B = 1 call, so two idle waves in its last block).  Batch 0
+    direct-load kernel (D = 24, H = 3: 6 items in the B = 1 call, so two idle waves in its last block; D = 16 and 96
+    at H = 8, ViT-B's motion modules).  Batch 0
     is all NaN: batch 1 is finite, inside the bound and bit-identical to the B = 1 call on batch 1 alone; both
     outputs sit between sentinel guards."""
     T = tune_lib()

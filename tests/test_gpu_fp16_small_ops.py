@@ -319,6 +319,35 @@ def test_groupnorm_linear_edges(C, S, Fr):
     note(f"groupnorm_linear C={C} S={S} F={Fr}", worst)
 
 
+@pytest.mark.parametrize("C,S,Fr", [(384, 37, 3), (768, 19, 5)])
+def test_groupnorm_linear_unfused_vitb_widths(C, S, Fr):
+    """ViT-B's motion modules 0 and 1 (C = N = 384 and 768, 12 and 24 channels per group): no fused kernel
+    (vda_groupnorm_linear_fused says 0), so ops.groupnorm_linear is GroupNorm into a workspace + vda_gemm on the same
+    fp16 operand.  The output under groupnorm_linear_ref_bound and bit-identical to ops.groupnorm + ops.gemm;
+    stats_out ([M, ceil(N / 256), 2], the last part of C = 384 is 128 columns wide) against float64 sums of the stored
+    rows, with a NaN guard row after row M - 1; the middle frame carries the +40 offset."""
+    assert lib().vda_groupnorm_linear_fused(C, 32, C) == 0
+    x = fb.gn_case(Fr, S, C, seed=3)
+    M, P = Fr * S, (C + 255) // 256
+    g, b = fb.gn_affine(C, seed=C)
+    w, bias = fb.rnd16(C, C, scale=C ** -0.5, seed=C + 1), fb.rnd32(C, scale=0.1, seed=C + 2)
+    ref, bound = fb.groupnorm_linear_ref_bound(x, g, b, 32, 1e-6, w, bias)
+    xh, gd, bd, wd, biasd = h(x.view(-1, C)), f32(g), f32(b), h(w), f32(bias)
+    st = torch.full((M + 1, P, 2), float("nan"), device=DEV)
+    y = ops.groupnorm_linear(xh, gd, bd, Fr, 32, 1e-6, wd, bias=biasd, stats_out=st)
+    what = f"groupnorm_linear unfused C={C} S={S} F={Fr}"
+    worst = assert_elementwise(y, ref, bound, what)
+    assert rel(y, ref) < BAR, what
+    assert torch.equal(y, ops.gemm(ops.groupnorm(xh, gd, bd, Fr, 32, 1e-6), wd, bias=biasd)), f"{what}: not the composition"
+    assert torch.equal(y, ops.groupnorm_linear(xh, gd, bd, Fr, 32, 1e-6, wd, bias=biasd)), f"{what}: not deterministic"
+    ypad = torch.zeros(M, P * 256, dtype=torch.float16)  # zero columns add nothing to a part's sums
+    ypad[:, :C] = y.cpu()
+    sref, sbound = fb.row_stats_ref_bound(ypad)
+    ws = assert_elementwise(st[:M], sref, sbound, what + " stats_out")
+    assert bool(torch.isnan(st[M]).all()), f"{what}: stats_out written past row M - 1"
+    note(f"{what} (stats {ws:.3f})", worst)
+
+
 def test_groupnorm_linear_outlier_frame():
     """The fused operand built from the repaired statistics: frame 1 of 2 carries the first-position outlier at
     74 x 74 x 256; M = 10,952 rows, where the composition's GEMM is the phased kernel: bit-identical."""
