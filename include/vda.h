@@ -471,6 +471,62 @@ int vda_depth_colorize(const float* depth, int32_t F, int32_t H, int32_t W, cons
                        const uint8_t* lut, int32_t layout, uint8_t* out, void* stream);
 
 /*
+ * Point clouds on the device (the reference's project_image_to_pointcloud / project_scene_to_3d,
+ * datasets/visualisation_utils.py:82-187, which go through Open3D on the host): metric depth through the
+ * pinhole intrinsics and one affine matrix per frame to a dense, ordered list of 3-D points, as tensors or as
+ * the body of a binary PLY.  An order-preserving stream compaction fused with the unprojection, in two calls.
+ * No atomics, no allocation, no synchronisation; results stay on the device; argument checks (-22) run before
+ * any launch.
+ *
+ * Operands: depth [F, H, W] float (metres, 4-byte aligned); valid [F, H, W] uint8 (non-zero = valid) or NULL
+ * (all valid, as in the reference, whose mask line is commented out); rgb [F, H, W, 3] uint8 or NULL;
+ * K [F, 4] float = (fx, fy, cx, cy); M [F, 3, 4] float, row-major camera-to-output, or NULL (none).
+ * 1 <= F <= 65535 (the launch grid), H, W, step >= 1, at most 2^31 - 1 candidates per frame.
+ * Candidates of frame f: the pixels (i, j) with i % step == 0 and j % step == 0, row-major, frames in index
+ * order.  A candidate is kept when (valid == NULL || valid[f,i,j] != 0) && d > 0.0f && d < trunc, d =
+ * depth[f,i,j]: NaN, +-Inf, zero and negative depths fail the compares; they are selected out, never
+ * multiplied out.  trunc: the reference passes the double max_depth - 1e-4 to Open3D, which compares the
+ * float pixel against it; pass the smallest float >= that double and the fp32 compare decides the same.
+ * Point of a kept candidate, every operation one correctly rounded fp32 operation (IEEE division, no
+ * reciprocal, no contraction), with the original i and j:
+ *   z = d;  x = ((float)j - cx) * z / fx;  y = ((float)i - cy) * z / fy
+ *   out_r = ((M[r][0]*x + M[r][1]*y) + M[r][2]*z) + M[r][3],  r = 0, 1, 2        (M == NULL: x, y, z)
+ * so the result equals the separate torch fp32 ops bit for bit.  Colour: the three bytes of rgb[f,i,j].
+ * Deviation: Open3D computes in double and divides by the homogeneous w; here M is affine and fp32.
+ * The kept points are output densely in candidate order.  The same input gives the same bytes on every run,
+ * and frame f of an [F] call gets the bits of a single-frame call on it.
+ *
+ * vda_cloud_count: a block owns one contiguous run of vda_cloud_span() candidates of one frame and counts
+ *   the ones it keeps; a scan per frame and one over the frames give frame_offsets [F + 1] int64 (DEVICE,
+ *   8-byte aligned) = the exclusive prefix of the frames' counts, frame_offsets[F] = the total N.
+ *   ws: exactly vda_cloud_workspace(F, H, W, step) bytes of device memory owned by the caller, 8-byte
+ *   aligned; it needs no initialisation.  Unlike the other workspaces of this library it CARRIES STATE: count
+ *   leaves every block's output offset in it and vda_cloud_write reads them, so hand the same, untouched ws
+ *   (and the same depth, valid, F, H, W, step, trunc) to write.
+ * vda_cloud_write: recomputes the predicate, ranks the kept lanes of a wave with the 64-bit ballot, adds the
+ *   wave bases through LDS and the block's offset from ws, and stores the points with index < cap only:
+ *   nothing is written at or past cap (cap >= 0; cap = N writes everything) and nothing outside the output.
+ *     VDA_CLOUD_SPLIT    out float [cap, 3] (4-byte aligned) and, with rgb, out_rgb uint8 [cap, 3] (any
+ *                        address; must be non-NULL when rgb is)
+ *     VDA_CLOUD_PACKED   out = cap records of 12 bytes (float x y z) or, with rgb, 15 bytes (float x y z,
+ *                        uchar r g b), little-endian: the body of a binary PLY.  out may have ANY byte
+ *                        alignment; out_rgb is not used.
+ *   A block's records are staged in LDS and leave as one contiguous byte run: bytes up to the first dword
+ *   boundary, dword stores, bytes after the last one.
+ */
+enum {
+  VDA_CLOUD_SPLIT = 0,
+  VDA_CLOUD_PACKED = 1
+};
+int64_t vda_cloud_workspace(int32_t F, int32_t H, int32_t W, int32_t step);
+int64_t vda_cloud_span(void);
+int vda_cloud_count(const float* depth, const uint8_t* valid, int32_t F, int32_t H, int32_t W, int32_t step,
+                    float trunc, int64_t* frame_offsets, void* ws, int64_t ws_bytes, void* stream);
+int vda_cloud_write(const float* depth, const uint8_t* valid, const uint8_t* rgb, int32_t F, int32_t H, int32_t W,
+                    int32_t step, float trunc, const float* K, const float* M, int32_t layout, void* out,
+                    uint8_t* out_rgb, int64_t cap, const void* ws, int64_t ws_bytes, void* stream);
+
+/*
  * Ground-truth comparison video on the device (the reference's calculate_metrics.py:206-258 with
  * utils/vis_util.py: visualise_data): per frame a canvas of rows x cols tiles of H x W pixels, the RGB frame,
  * the GT depth, and per method an error map |gt - pred|, the prediction and a "stability" image (the x-t

@@ -31,6 +31,7 @@ EXPORTED = (
     "vda_scale_shift", "vda_scale_shift_workspace", "vda_depth_align",
     "vda_depth_eval_workspace", "vda_depth_eval_fit", "vda_depth_eval_metrics",
     "vda_depth_range_workspace", "vda_depth_range", "vda_depth_colorize_bytes", "vda_depth_colorize",
+    "vda_cloud_workspace", "vda_cloud_span", "vda_cloud_count", "vda_cloud_write",
     "vda_tile_size", "vda_depth_absdiff_range_workspace", "vda_depth_absdiff_range", "vda_panel_compose_bytes",
     "vda_panel_compose",
     "vda_yuv_to_rgb", "vda_preprocess_yuv_workspace", "vda_preprocess_yuv",
@@ -48,6 +49,7 @@ ACT_NONE, ACT_GELU, ACT_GEGLU, ACT_RELU, ACT_SWIGLU = 0, 1, 2, 3, 4
 STORE_ROWS, STORE_PIXEL_SHUFFLE = 0, 1
 VIS_INDEX, VIS_HWC, VIS_PLANAR444, VIS_PLANAR420 = 0, 1, 2, 3  # VDA_VIS_* (vda_depth_colorize layouts)
 TILE_RGB, TILE_DEPTH, TILE_ERROR, TILE_XT = 0, 1, 2, 3  # VDA_TILE_* (vda_panel_compose tile kinds)
+CLOUD_SPLIT, CLOUD_PACKED = 0, 1  # VDA_CLOUD_* (vda_cloud_write layouts)
 YUV_420, YUV_422, YUV_444, YUV_MONO = 0, 1, 2, 3  # VDA_YUV_* (vda_yuv_to_rgb / vda_preprocess_yuv chroma codes)
 
 
@@ -125,6 +127,10 @@ def _declare(lib):
         "vda_depth_range": ([P, L, P, P, L, P], I),
         "vda_depth_colorize_bytes": ([I, I, I, I], L),
         "vda_depth_colorize": ([P, I, I, I, P, P, I, P, P], I),
+        "vda_cloud_workspace": ([I, I, I, I], L),
+        "vda_cloud_span": ([], L),
+        "vda_cloud_count": ([P, P, I, I, I, I, F, P, P, L, P], I),
+        "vda_cloud_write": ([P, P, P, I, I, I, I, F, P, P, I, P, P, L, P, L, P], I),
         "vda_tile_size": ([], L),
         "vda_depth_absdiff_range_workspace": ([L], L),
         "vda_depth_absdiff_range": ([P, P, P, L, P, P, L, P], I),

@@ -706,6 +706,79 @@ Tensor depth_colorize(const Tensor& depth, const Tensor& range, OptT lut, int64_
   return out;
 }
 
+// ---- point clouds ----------------------------------------------------------------------------------
+// depth [F, H, W] float, valid [F, H, W] uint8 and rgb [F, H, W, 3] uint8 on depth's device.
+void cloud_inputs(const char* op, const Tensor& depth, OptT valid, int64_t step) {
+  TORCH_CHECK(depth.scalar_type() == at::kFloat && depth.dim() == 3 && depth.is_contiguous() && depth.numel() >= 1,
+              "vda ", op, ": depth must be a contiguous, non-empty float [F, H, W] tensor");
+  TORCH_CHECK(depth.size(0) <= 65535, "vda ", op, ": F <= 65535 frames per call, got ", depth.size(0));
+  TORCH_CHECK(depth.size(1) <= INT32_MAX && depth.size(2) <= INT32_MAX, "vda ", op, ": H and W must fit 32 bits");
+  TORCH_CHECK(step >= 1 && step <= INT32_MAX, "vda ", op, ": step must be at least 1, got ", step);
+  if (valid) {
+    need_contig(*valid, at::kByte, "valid", depth);
+    TORCH_CHECK(valid->sizes() == depth.sizes(), "vda ", op, ": valid must have depth's shape");
+  }
+}
+
+// -> (frame_offsets [F + 1] int64, ws): ws carries the block offsets to cloud_write.
+std::tuple<Tensor, Tensor> cloud_count(const Tensor& depth, OptT valid, int64_t step, double trunc) {
+  cloud_inputs("cloud_count", depth, valid, step);
+  const int64_t F = depth.size(0), H = depth.size(1), W = depth.size(2);
+  const int64_t wsb = vda_cloud_workspace((int32_t)F, (int32_t)H, (int32_t)W, (int32_t)step);
+  Tensor offs = at::empty({F + 1}, depth.options().dtype(at::kLong));
+  Tensor ws = at::empty({wsb}, depth.options().dtype(at::kByte));
+  if (depth.is_meta()) return {offs, ws};
+  const at::OptionalDeviceGuard g(depth.device());
+  check_rc(vda_cloud_count((const float*)depth.data_ptr(), (const uint8_t*)ptr(valid), (int32_t)F, (int32_t)H,
+                           (int32_t)W, (int32_t)step, (float)trunc, (int64_t*)offs.data_ptr(), ws.data_ptr(), wsb,
+                           stream_of(depth)),
+           "vda_cloud_count");
+  return {offs, ws};
+}
+
+// n: the number of points (frame_offsets[F] of cloud_count, read by the caller), which sizes the output.
+// VDA_CLOUD_SPLIT -> (points [n, 3] float, colors [n, 3] uint8 or None); VDA_CLOUD_PACKED -> (the n records as
+// [n * 12] or [n * 15] uint8, None).
+std::tuple<Tensor, optional<Tensor>> cloud_write(const Tensor& depth, OptT valid, OptT rgb, const Tensor& K, OptT M,
+                                                 int64_t step, double trunc, int64_t layout, const Tensor& ws,
+                                                 int64_t n) {
+  cloud_inputs("cloud_write", depth, valid, step);
+  const int64_t F = depth.size(0), H = depth.size(1), W = depth.size(2);
+  if (rgb) {
+    need_contig(*rgb, at::kByte, "rgb", depth);
+    TORCH_CHECK(rgb->dim() == 4 && rgb->size(0) == F && rgb->size(1) == H && rgb->size(2) == W && rgb->size(3) == 3,
+                "vda cloud_write: rgb must be [F, H, W, 3]");
+  }
+  need_contig(K, at::kFloat, "K", depth);
+  TORCH_CHECK(K.dim() == 2 && K.size(0) == F && K.size(1) == 4, "vda cloud_write: K must be [F, 4] = (fx, fy, cx, cy)");
+  if (M) {
+    need_contig(*M, at::kFloat, "M", depth);
+    TORCH_CHECK(M->dim() == 3 && M->size(0) == F && M->size(1) == 3 && M->size(2) == 4,
+                "vda cloud_write: M must be [F, 3, 4]");
+  }
+  TORCH_CHECK(layout == VDA_CLOUD_SPLIT || layout == VDA_CLOUD_PACKED, "vda cloud_write: unknown layout ", layout);
+  TORCH_CHECK(n >= 0, "vda cloud_write: n must not be negative, got ", n);
+  need_contig(ws, at::kByte, "ws", depth);
+  const int64_t wsb = vda_cloud_workspace((int32_t)F, (int32_t)H, (int32_t)W, (int32_t)step);
+  TORCH_CHECK(ws.numel() == wsb, "vda cloud_write: ws must be the workspace cloud_count returned for this shape");
+  Tensor out;
+  optional<Tensor> colors;
+  if (layout == VDA_CLOUD_PACKED) {
+    out = at::empty({n * (rgb ? 15 : 12)}, depth.options().dtype(at::kByte));
+  } else {
+    out = at::empty({n, 3}, depth.options());
+    if (rgb) colors = at::empty({n, 3}, depth.options().dtype(at::kByte));
+  }
+  if (depth.is_meta() || n == 0) return {out, colors};
+  const at::OptionalDeviceGuard g(depth.device());
+  check_rc(vda_cloud_write((const float*)depth.data_ptr(), (const uint8_t*)ptr(valid), (const uint8_t*)ptr(rgb),
+                           (int32_t)F, (int32_t)H, (int32_t)W, (int32_t)step, (float)trunc, (const float*)K.data_ptr(),
+                           (const float*)ptr(M), (int32_t)layout, out.data_ptr(),
+                           colors ? (uint8_t*)colors->data_ptr() : nullptr, n, ws.data_ptr(), wsb, stream_of(depth)),
+           "vda_cloud_write");
+  return {out, colors};
+}
+
 // ---- ground-truth comparison video ---------------------------------------------------------------
 Tensor depth_absdiff_range(const Tensor& a, const Tensor& b, OptT valid) {
   TORCH_CHECK(a.scalar_type() == at::kFloat && a.is_contiguous() && a.numel() >= 1,
@@ -941,6 +1014,9 @@ TORCH_LIBRARY(vda, m) {
   m.def("depth_eval_fit(Tensor pred, Tensor gt, Tensor? valid=None, bool per_frame=False) -> (Tensor ss, Tensor sums)");
   m.def("depth_eval_metrics(Tensor pred, Tensor gt, Tensor? valid, Tensor ss, float max_depth=80., "
         "bool want_aligned=False) -> (Tensor frame_sums, Tensor total, Tensor? aligned)");
+  m.def("cloud_count(Tensor depth, Tensor? valid, int step, float trunc) -> (Tensor frame_offsets, Tensor ws)");
+  m.def("cloud_write(Tensor depth, Tensor? valid, Tensor? rgb, Tensor K, Tensor? M, int step, float trunc, int layout, "
+        "Tensor ws, int n) -> (Tensor out, Tensor? colors)");
 }
 
 #define VDA_IMPL(KEY)                                         \
@@ -965,6 +1041,8 @@ TORCH_LIBRARY(vda, m) {
     m.impl("depth_align", &depth_align);                      \
     m.impl("depth_eval_fit", &depth_eval_fit);                \
     m.impl("depth_eval_metrics", &depth_eval_metrics);        \
+    m.impl("cloud_count", &cloud_count);                      \
+    m.impl("cloud_write", &cloud_write);                      \
     m.impl("depth_range", &depth_range);                      \
     m.impl("depth_colorize", &depth_colorize);                \
     m.impl("depth_absdiff_range", &depth_absdiff_range);      \

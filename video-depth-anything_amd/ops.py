@@ -328,6 +328,69 @@ def depth_eval_metrics(pred: Tensor, gt: Tensor, valid: Optional[Tensor], ss: Te
     return _vda().depth_eval_metrics(pred, gt, valid, ss, float(max_depth), bool(want_aligned))
 
 
+CLOUD_LAYOUTS = {"split": _lib.CLOUD_SPLIT, "packed": _lib.CLOUD_PACKED}
+
+
+def _cloud_inputs(depth: Tensor, valid: Optional[Tensor], step: int, trunc: float):
+    """Checks shared by the point-cloud ops; returns ``valid`` as uint8 (a bool mask is viewed, not copied)."""
+    if not isinstance(depth, torch.Tensor) or not depth.is_cuda or depth.dtype != torch.float32:
+        raise ValueError("depth must be a float32 GPU tensor (no CPU path in the product)")
+    if depth.dim() != 3 or depth.numel() < 1 or not depth.is_contiguous() or depth.shape[0] > 65535:
+        raise ValueError(f"depth must be contiguous, non-empty [F, H, W] with F <= 65535, got {tuple(depth.shape)}")
+    if int(step) != step or int(step) < 1:
+        raise ValueError(f"step must be an integer >= 1, got {step!r}")
+    if float(trunc) != float(torch.tensor(float(trunc), dtype=torch.float32)):
+        raise ValueError(f"trunc must be exactly representable in float32, got {trunc!r}")
+    if valid is not None:
+        if not isinstance(valid, torch.Tensor) or valid.dtype not in (torch.bool, torch.uint8):
+            raise ValueError("valid must be a bool or uint8 tensor")
+        if valid.shape != depth.shape or valid.device != depth.device or not valid.is_contiguous():
+            raise ValueError(f"valid must be contiguous with depth's shape and device, got {tuple(valid.shape)} on {valid.device}")
+        if valid.dtype == torch.bool:
+            valid = valid.view(torch.uint8)
+    return valid
+
+
+def cloud_count(depth: Tensor, valid: Optional[Tensor] = None, *, step: int = 1, trunc: float):
+    """Count the points ``cloud_write`` will produce: depth [F, H, W] fp32 on the GPU, ``valid`` bool / uint8 of
+    the same shape or None -> (frame_offsets [F + 1] int64 on the device, the exclusive prefix of the frames'
+    counts with the total last, and ws, the workspace that carries the block offsets to ``cloud_write``).  A
+    candidate (every ``step``-th row and column) is kept when it is valid and ``0 < depth < trunc``.  No host
+    sync (vda.h vda_cloud_count)."""
+    valid = _cloud_inputs(depth, valid, step, trunc)
+    return _vda().cloud_count(depth, valid, int(step), float(trunc))
+
+
+def cloud_write(depth: Tensor, valid: Optional[Tensor], rgb: Optional[Tensor], K: Tensor, M: Optional[Tensor], *,
+                step: int = 1, trunc: float, ws: Tensor, n: int, layout="split"):
+    """Unproject and compact the kept candidates of ``cloud_count``'s operands (the same depth, valid, step and
+    trunc, and its ws) in candidate order: ``K`` [F, 4] fp32 = (fx, fy, cx, cy), ``M`` [F, 3, 4] fp32
+    camera-to-output or None, ``rgb`` [F, H, W, 3] uint8 or None, ``n`` the number of points to store (the total
+    ``frame_offsets[-1]``, or fewer: only the first ``n`` are written).  ``layout="split"`` -> (points [n, 3]
+    fp32, colors [n, 3] uint8 or None); ``"packed"`` -> (the records of a binary PLY body, [n * 12] or [n * 15]
+    uint8, None) (vda.h vda_cloud_write)."""
+    valid = _cloud_inputs(depth, valid, step, trunc)
+    F, H, W = depth.shape
+    if rgb is not None:
+        if not isinstance(rgb, torch.Tensor) or rgb.dtype != torch.uint8 or rgb.device != depth.device \
+                or tuple(rgb.shape) != (F, H, W, 3) or not rgb.is_contiguous():
+            raise ValueError("rgb must be a contiguous uint8 [F, H, W, 3] tensor on depth's device")
+    for name, t, shape in (("K", K, (F, 4)), ("M", M, (F, 3, 4))):
+        if t is None and name == "M":
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != depth.device \
+                or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous float32 {list(shape)} tensor on depth's device")
+    code = CLOUD_LAYOUTS.get(layout, layout) if isinstance(layout, str) else int(layout)
+    if code not in CLOUD_LAYOUTS.values():
+        raise ValueError(f"layout must be one of {sorted(CLOUD_LAYOUTS)}, got {layout!r}")
+    if not isinstance(ws, torch.Tensor) or ws.dtype != torch.uint8 or ws.device != depth.device:
+        raise ValueError("ws must be the uint8 workspace cloud_count returned")
+    if int(n) != n or int(n) < 0:
+        raise ValueError(f"n must be a non-negative integer, got {n!r}")
+    return _vda().cloud_write(depth, valid, rgb, K, M, int(step), float(trunc), code, ws, int(n))
+
+
 VIS_LAYOUTS = {"index": _lib.VIS_INDEX, "hwc": _lib.VIS_HWC, "planar444": _lib.VIS_PLANAR444,
                "planar420": _lib.VIS_PLANAR420}
 
